@@ -27,6 +27,13 @@ subscriber IPs (SNAT + QoS + antispoof path), 10% DHCP DISCOVER/REQUEST
 blocks / QoS buckets / antispoof bindings, random-init, sharded by the
 MAC/IP hashring when N>1.
 
+A plain run sets up, warms up, times --steps steps and prints the result
+line (Mpps, ms_per_step).  --full adds the secondary phases after the
+timed steps: launched-batch DHCP OFFER p50/p99, the downlink return
+path, persistent-service latency and the host-boundary conveyor; without
+it their result fields are null.  --dump-outputs DIR writes what the
+last timed step returned as .npy files (see dump_outputs).
+
 vs_baseline: the reference's published Mpps figure on this metric is the
 XDP single-core packet rate it cites (24 Mpps/core, BASELINE.md "XDP
 single-core packet rate"); its DHCP-specific ceiling is 1-2 Mpps
@@ -406,6 +413,39 @@ def host_io_dhcp_latency(launcher, args, now_sec, reps=64):
     return lats[len(lats) // 2], lats[int(len(lats) * 0.99)]
 
 
+DUMP_PACKET_ROWS = 8192
+
+
+def dump_outputs(out_dir, last, rank, world):
+    """Write what the last timed step returned to its caller as
+    <out_dir>/<name>.npy (float32; rank-suffixed when world>1):
+    `verdict` and `out_len` for every packet of the batch, and
+    `packets`, a fixed seeded sample of DUMP_PACKET_ROWS full stride-wide
+    rows of the in-place rewritten batch (`packet_rows` names them) —
+    the whole 1M x 512 B batch would be 2 GB as float32, the sample
+    keeps a dump near 25 MB.  Inputs, tables and the sample are all
+    seeded, so two runs with the same arguments are comparable file by
+    file."""
+    import torch
+    d, v, ol = last
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    m = v.numel()
+    rows = np.sort(np.random.default_rng(0xD0C5).choice(
+        m, size=min(m, DUMP_PACKET_ROWS), replace=False))
+    rows_dev = torch.from_numpy(rows).to(d.device)
+    outs = {
+        "verdict": v.cpu().numpy(),
+        "out_len": ol.cpu().numpy(),
+        "packet_rows": rows.astype(np.float64),
+        "packets": d[:m].index_select(0, rows_dev).cpu().numpy(),
+    }
+    for name, arr in outs.items():
+        if arr.dtype != np.float64:
+            arr = arr.astype(np.float32)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,6 +456,17 @@ def main():
     ap.add_argument("--subs", type=int, default=1_000_000)
     ap.add_argument("--dhcp-frac", type=float, default=0.1)
     ap.add_argument("--stride", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary "
+                         "phases (launched-batch DHCP latency, downlink "
+                         "return path, persistent-service latency, "
+                         "host-boundary conveyor); a plain run measures "
+                         "the headline only and reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed "
+                         "step returned (verdict, out_len, a fixed seeded "
+                         "sample of the rewritten packet rows) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--lat-batch", type=int, default=2048)
     ap.add_argument("--lat-reps", type=int, default=64)
     ap.add_argument("--no-latency", action="store_true")
@@ -486,6 +537,10 @@ def main():
     # (same-box A/B: nbuf 2/3/4 -> 1537/1555/1567 Mpps); BNG_NBUF
     # overrides for experiments
     nbuf = (int(os.environ.get("BNG_NBUF", "4")) if overlap else 1)
+    if args.dump_outputs and overlap and nbuf < 2:
+        # with one buffer the next batch's RX copy lands on the last
+        # step's packets before they can be written out
+        ap.error("--dump-outputs with overlap needs BNG_NBUF >= 2")
     works = [torch.empty_like(pristine) for _ in range(nbuf)]
     clss = [torch.empty(args.batch, dtype=torch.uint8, device=device)
             for _ in range(nbuf)]
@@ -539,14 +594,19 @@ def main():
             batches[b] = (d, l, o)
             prep_done[b].record(prep_stream)
 
+    # what the latest step handed back to its caller: (packets rewritten
+    # in place, verdict, out_len) — kept for --dump-outputs
+    last = [None]
+
     def step(now_ns, k=0):
         cur = torch.cuda.current_stream(device)
         if overlap:
             b = k % nbuf
             cur.wait_event(prep_done[b])
             d, l, o = batches[b]
-            launcher.uplink(d, l, now_ns=now_ns, now_sec=now_sec,
-                            sort_by_type=not args.no_sort, order=o)
+            v, ol = launcher.uplink(d, l, now_ns=now_ns, now_sec=now_sec,
+                                    sort_by_type=not args.no_sort, order=o)
+            last[0] = (d, v, ol)
             work_free[b].record(cur)
             prep(k + 1)                            # overlap next batch
             return
@@ -555,8 +615,9 @@ def main():
         if distributed:
             owner = launcher.shard_owner(d, l, world)
             d, l = exchange(d, l, owner)
-        launcher.uplink(d, l, now_ns=now_ns, now_sec=now_sec,
-                        sort_by_type=not args.no_sort)
+        v, ol = launcher.uplink(d, l, now_ns=now_ns, now_sec=now_sec,
+                                sort_by_type=not args.no_sort)
+        last[0] = (d, v, ol)
     if overlap:
         prep(0)
 
@@ -586,9 +647,13 @@ def main():
     mpps = total_pkts / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], rank, world)
+
+    # everything below is secondary to the headline: --full only
     # p50 DHCP OFFER latency: small all-DHCP batches, submit -> reply ready
     p50_us = p99_us = None
-    if not args.no_latency and rank == 0:
+    if args.full and not args.no_latency and rank == 0:
         lat_np, lat_lens_np = gen_batch(args.lat_batch, args.subs, 1.0,
                                         args.stride, seed=777)
         lp = torch.from_numpy(lat_np).to(device)
@@ -617,7 +682,7 @@ def main():
     # fused DNAT + egress-QoS pipeline (driver-visible counterpart of
     # the uplink headline)
     downlink_mpps = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             recs = launcher.export_nat_sessions()
             if len(recs) >= 1000:
@@ -665,7 +730,7 @@ def main():
     # 453us; the resident waves own their CU so the flood cannot starve
     # them)
     svc_lat = None
-    if not args.no_latency and rank == 0 and world == 1:
+    if args.full and not args.no_latency and rank == 0 and world == 1:
         try:
             flood = lambda: step(base_ns, args.warmup + args.steps)  # noqa: E731,E501
             q50, q99 = service_latency(launcher, args, now_sec)
@@ -694,7 +759,7 @@ def main():
     # pipeline rate).  world==1 only: each GPU has its own PCIe link, so
     # the per-GPU host-fed rate is the scaling unit.
     hostio = None
-    if not args.no_host_io and rank == 0 and world == 1:
+    if args.full and not args.no_host_io and rank == 0 and world == 1:
         hm, per_step, pipe_lat = host_io_phase(
             launcher, pristine, lens, lens_np, args, now_sec,
             args.host_io_steps, args.host_io_warmup)
