@@ -76,7 +76,9 @@ BNG_DEV void bng_zero(uint8_t* p, int n) {
 /* ------------------------------------------------ wave-aggregated stats */
 /* One atomicAdd per wave instead of per lane: a single contended counter
  * word saturates at ~88 atomics/us on MI355X (microarch 'dequeue' row) —
- * per-lane atomics would cap the chip at ~88 Mpps per counter. */
+ * per-lane atomics would cap the chip at ~88 Mpps per counter.  Used by
+ * the persistent DHCP service (publishes per served batch) and the NAT
+ * sweep; the batched packet kernels aggregate per block (below). */
 BNG_DEV void stat_inc(unsigned long long* counter, bool cond) {
   uint64_t mask = __ballot(cond);
   if (mask == 0) return;
@@ -86,15 +88,52 @@ BNG_DEV void stat_inc(unsigned long long* counter, bool cond) {
     atomicAdd(counter, (unsigned long long)__popcll(mask));
 }
 
-BNG_DEV void stat_add(unsigned long long* counter, uint64_t v, bool cond) {
-  /* wave-reduce v (0 where !cond), one atomic per wave */
-  uint64_t x = cond ? v : 0;
+/* ----------------------------------------------- block-aggregated stats */
+/* The batched packet kernels commit once per BLOCK, not per wave: a 1M
+ * batch is 16 384 waves, and four counters per data wave put ~60 k
+ * atomics per launch on a handful of cache lines that serialise at the
+ * memory side.  At the end of each grid-stride iteration a wave counts
+ * each flag (popcount of a ballot is scalar) and one lane adds the
+ * non-zero counts to a small __shared__ array with LDS atomics — running
+ * counts held in registers across the loop spilled in the fused uplink
+ * kernel, the LDS array costs no registers.  After the loop and one
+ * barrier the first threads of the block issue one global atomic per
+ * non-zero counter.  Every helper below must be reached by all lanes of
+ * the wave (sb_zero / sb_commit by all threads of the block). */
+BNG_DEV uint32_t wave_count(bool cond) {
+  return (uint32_t)__popcll((unsigned long long)__ballot(cond));
+}
+
+/* wave sum of a per-lane u32 (callers pass <= 65535 per lane, so 64 lanes
+ * cannot overflow); the result is wave-uniform */
+BNG_DEV uint32_t wave_sum32(uint32_t v) {
   for (int off = 32; off > 0; off >>= 1)
-    x += __shfl_down((unsigned long long)x, off, 64);
-  uint64_t any = __ballot(cond);
-  int lane = threadIdx.x & 63;
-  if (lane == 0 && x) atomicAdd(counter, (unsigned long long)x);
-  (void)any;
+    v += __shfl_down(v, off, 64);
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+/* zero the block's shared counters; call first thing in the kernel */
+BNG_DEV void sb_zero(unsigned long long* sb, int n) {
+  if ((int)threadIdx.x < n) sb[threadIdx.x] = 0;
+  __syncthreads();
+}
+
+/* add one wave-uniform count to the block's shared counter */
+BNG_DEV void sb_fold(unsigned long long* sb, int slot, uint64_t cnt) {
+  if (cnt && (threadIdx.x & 63) == 0)
+    atomicAdd(&sb[slot], (unsigned long long)cnt);
+}
+
+/* after the folds and ONE __syncthreads(): thread base+k publishes shared
+ * slot base+k to global counter k — one device-scope atomic per non-zero
+ * counter per block */
+BNG_DEV void sb_commit(const unsigned long long* sb, int base, int n,
+                       unsigned long long* counters) {
+  int k = (int)threadIdx.x - base;
+  if (k >= 0 && k < n) {
+    unsigned long long v = sb[base + k];
+    if (v) atomicAdd(&counters[k], v);
+  }
 }
 
 /* --------------------------------------------- publish/consume protocol */

@@ -52,6 +52,8 @@ void bng_launch_nat_sweep(void*, uint32_t, void*, uint32_t, void*, uint32_t,
                           void*, hipStream_t);
 void bng_launch_shard_owner(const void*, const void*, void*, int, int, int,
                             hipStream_t);
+void bng_set_pkt_grid_cap(int);
+int bng_get_pkt_grid_cap(void);
 void bng_launch_dhcp_service(void*, void*, const void*, void*, void*, void*,
                              int, int, void*, const void*, uint32_t,
                              const void*, uint32_t, const void*, void*,
@@ -479,6 +481,16 @@ py::dict layout_report() {
   return d;
 }
 
+/* Grid cap (in 256-thread blocks) of the batched packet kernels; 0
+ * restores the built-in default.  The A/B knob for grid sizing, and the
+ * hook tests use to force several grid-stride iterations at tiny n. */
+void set_pkt_grid_cap(int64_t blocks) {
+  TORCH_CHECK(blocks >= 0 && blocks <= 65536, "blocks in [0,65536]");
+  bng_set_pkt_grid_cap((int)blocks);
+}
+
+int64_t get_pkt_grid_cap() { return bng_get_pkt_grid_cap(); }
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -520,4 +532,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("alloc_pinned_coherent", &alloc_pinned_coherent);
   m.def("dhcp_service_join", &dhcp_service_join);
   m.def("layout_report", &layout_report);
+  m.def("set_pkt_grid_cap", &set_pkt_grid_cap, py::arg("blocks"));
+  m.def("get_pkt_grid_cap", &get_pkt_grid_cap);
 }

@@ -13,8 +13,9 @@
  * Execution model: one thread per packet, grid-stride, 256-thread blocks
  * (4 waves).  Packet batches are fixed-stride slots in HBM; every lookup
  * table is an open-addressing HBM hash table (bng_abi.h).  Per-packet
- * ktime becomes one host-supplied batch timestamp.  Stats are wave-
- * aggregated before one device-scope atomic per wave (bng_device.h).
+ * ktime becomes one host-supplied batch timestamp.  Stats are counted
+ * per wave, summed per block in shared memory, and committed with one
+ * device-scope atomic per counter per block (bng_device.h).
  *
  * Differential-tested against bng_amd/dataplane/golden.py on random
  * batches (tests/test_kernels_gpu.py).
@@ -608,6 +609,32 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
   return BNG_TX;
 }
 
+/* Layout of the per-block shared counter array the batched packet kernels
+ * aggregate into (bng_device.h sb_*): the four global stat arrays back to
+ * back, each group in its ABI enum order. */
+enum {
+  SB_DHCP = 0,
+  SB_NAT = SB_DHCP + BNG_DHCP_NSTATS,
+  SB_AS = SB_NAT + BNG_NAT_NSTATS,
+  SB_QOS = SB_AS + BNG_AS_NSTATS,
+  SB_N = SB_QOS + BNG_QOS_NSTATS
+};
+
+/* end of one grid-stride iteration: count each flag over the wave and
+ * add it to the block's shared counters */
+BNG_DEV void dhcp_count_stats(const dhcp_flags& F, unsigned long long* sb) {
+  sb_fold(sb, SB_DHCP + BNG_ST_VLAN_PACKETS, wave_count(F.vlan));
+  sb_fold(sb, SB_DHCP + BNG_ST_TOTAL_REQUESTS, wave_count(F.total));
+  sb_fold(sb, SB_DHCP + BNG_ST_FASTPATH_HITS, wave_count(F.hit));
+  sb_fold(sb, SB_DHCP + BNG_ST_FASTPATH_MISSES, wave_count(F.miss));
+  sb_fold(sb, SB_DHCP + BNG_ST_CACHE_EXPIRED, wave_count(F.expired));
+  sb_fold(sb, SB_DHCP + BNG_ST_ERRORS, wave_count(F.error));
+  sb_fold(sb, SB_DHCP + BNG_ST_OPTION82_PRESENT, wave_count(F.o82));
+  sb_fold(sb, SB_DHCP + BNG_ST_BROADCAST_REPLIES, wave_count(F.bcast));
+  sb_fold(sb, SB_DHCP + BNG_ST_UNICAST_REPLIES, wave_count(F.ucast));
+}
+
+/* per-wave commit: the persistent service publishes per served batch */
 BNG_DEV void dhcp_commit_stats(const dhcp_flags& F, unsigned long long* st) {
   stat_inc(&st[BNG_ST_VLAN_PACKETS], F.vlan);
   stat_inc(&st[BNG_ST_TOTAL_REQUESTS], F.total);
@@ -631,6 +658,8 @@ __global__ void dhcp_fastpath_kernel(
     const uint64_t* __restrict__ now_ptr) {
   if (now_ptr) now_sec = now_ptr[1];
   dhcp_tables T{subs, sub_mask, pools, n_pools, cfg, stats, now_sec};
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
   for (int base = 0; base < n; base += nthreads) {
@@ -643,8 +672,10 @@ __global__ void dhcp_fastpath_kernel(
       verdict[pid] = (uint8_t)v;
       out_len[pid] = ol;
     }
-    dhcp_commit_stats(F, stats);
+    dhcp_count_stats(F, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_DHCP, BNG_DHCP_NSTATS, stats);
 }
 
 /* ------------------------------------------- persistent DHCP service.
@@ -1224,18 +1255,18 @@ BNG_DEV int nat_ingress_process(pktctx& c, const nat_tables& T, nat_flags& F) {
   return BNG_FWD;
 }
 
-BNG_DEV void nat_commit_stats(const nat_flags& F, unsigned long long* st) {
-  stat_inc(&st[BNG_NS_SNAT], F.snat);
-  stat_inc(&st[BNG_NS_DNAT], F.dnat);
-  stat_inc(&st[BNG_NS_HAIRPIN], F.hairpin);
-  stat_inc(&st[BNG_NS_DROPPED], F.dropped);
-  stat_inc(&st[BNG_NS_PASSED], F.passed);
-  stat_inc(&st[BNG_NS_SESS_CREATED], F.sess_created);
-  stat_inc(&st[BNG_NS_SESS_EXPIRED], F.sess_expired);
-  stat_inc(&st[BNG_NS_PORT_EXHAUSTION], F.port_exh);
-  stat_inc(&st[BNG_NS_EIM_HITS], F.eim_hit);
-  stat_inc(&st[BNG_NS_EIM_MISSES], F.eim_miss);
-  stat_inc(&st[BNG_NS_ALG_TRIGGERS], F.alg);
+BNG_DEV void nat_count_stats(const nat_flags& F, unsigned long long* sb) {
+  sb_fold(sb, SB_NAT + BNG_NS_SNAT, wave_count(F.snat));
+  sb_fold(sb, SB_NAT + BNG_NS_DNAT, wave_count(F.dnat));
+  sb_fold(sb, SB_NAT + BNG_NS_HAIRPIN, wave_count(F.hairpin));
+  sb_fold(sb, SB_NAT + BNG_NS_DROPPED, wave_count(F.dropped));
+  sb_fold(sb, SB_NAT + BNG_NS_PASSED, wave_count(F.passed));
+  sb_fold(sb, SB_NAT + BNG_NS_SESS_CREATED, wave_count(F.sess_created));
+  sb_fold(sb, SB_NAT + BNG_NS_SESS_EXPIRED, wave_count(F.sess_expired));
+  sb_fold(sb, SB_NAT + BNG_NS_PORT_EXHAUSTION, wave_count(F.port_exh));
+  sb_fold(sb, SB_NAT + BNG_NS_EIM_HITS, wave_count(F.eim_hit));
+  sb_fold(sb, SB_NAT + BNG_NS_EIM_MISSES, wave_count(F.eim_miss));
+  sb_fold(sb, SB_NAT + BNG_NS_ALG_TRIGGERS, wave_count(F.alg));
 }
 
 __global__ void nat44_kernel(
@@ -1253,6 +1284,8 @@ __global__ void nat44_kernel(
   nat_tables T{sessions, sess_mask, reverse, rev_mask, eim, eim_mask,
                ctx, ctx_mask, cfg, hairpin_ips, n_hairpin, stats,
                log_ring, log_hdr, now_ns};
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
   for (int base = 0; base < n; base += nthreads) {
@@ -1265,13 +1298,28 @@ __global__ void nat44_kernel(
                         : nat_ingress_process(c, T, F);
       verdict[pid] = (uint8_t)v;
     }
-    nat_commit_stats(F, stats);
+    nat_count_stats(F, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_NAT, BNG_NAT_NSTATS, stats);
 }
 
 /* ============================================================ QoS  K3 */
 
 struct qos_flags { bool passed, dropped; uint32_t bytes; };
+
+/* byte sums keep a wave reduction (bytes is a frame length, <= 65535 per
+ * lane) and accumulate in 64 bits */
+BNG_DEV void qos_count_stats(const qos_flags& F, unsigned long long* sb) {
+  uint32_t np = wave_count(F.passed), nd = wave_count(F.dropped);
+  sb_fold(sb, SB_QOS + BNG_QS_PKT_PASSED, np);
+  sb_fold(sb, SB_QOS + BNG_QS_PKT_DROPPED, nd);
+  /* wave-uniform branches: every lane takes the reduction or none */
+  if (np) sb_fold(sb, SB_QOS + BNG_QS_BYTES_PASSED,
+                  wave_sum32(F.passed ? F.bytes : 0u));
+  if (nd) sb_fold(sb, SB_QOS + BNG_QS_BYTES_DROPPED,
+                  wave_sum32(F.dropped ? F.bytes : 0u));
+}
 
 /* Token-bucket check (ref token_bucket_check qos_ratelimit.c:70-104),
  * consume-first form: one atomicAdd(-len) when tokens suffice (the
@@ -1360,6 +1408,8 @@ __global__ void qos_kernel(
     uint8_t* __restrict__ verdict, int n, int stride, int is_egress,
     void* table, uint32_t mask,
     unsigned long long* stats, uint64_t now_ns) {
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
   for (int base = 0; base < n; base += nthreads) {
@@ -1378,16 +1428,23 @@ __global__ void qos_kernel(
       }
       verdict[pid] = (uint8_t)v;
     }
-    stat_inc(&stats[BNG_QS_PKT_PASSED], F.passed);
-    stat_inc(&stats[BNG_QS_PKT_DROPPED], F.dropped);
-    stat_add(&stats[BNG_QS_BYTES_PASSED], F.bytes, F.passed);
-    stat_add(&stats[BNG_QS_BYTES_DROPPED], F.bytes, F.dropped);
+    qos_count_stats(F, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_QOS, BNG_QOS_NSTATS, stats);
 }
 
 /* ====================================================== antispoof  K4 */
 
 struct as_flags { bool allowed, dropped, logged, v4viol, v6viol; };
+
+BNG_DEV void as_count_stats(const as_flags& F, unsigned long long* sb) {
+  sb_fold(sb, SB_AS + BNG_AS_ALLOWED, wave_count(F.allowed));
+  sb_fold(sb, SB_AS + BNG_AS_DROPPED, wave_count(F.dropped));
+  sb_fold(sb, SB_AS + BNG_AS_LOGGED, wave_count(F.logged));
+  sb_fold(sb, SB_AS + BNG_AS_V4_VIOLATIONS, wave_count(F.v4viol));
+  sb_fold(sb, SB_AS + BNG_AS_V6_VIOLATIONS, wave_count(F.v6viol));
+}
 
 BNG_DEV void spoof_log_push(bng_spoof_event* ring, bng_ring_header* hdr,
                             const uint8_t* mac, uint8_t proto,
@@ -1485,6 +1542,8 @@ __global__ void antispoof_kernel(
     const bng_antispoof_config* cfg,
     unsigned long long* stats,
     bng_spoof_event* ring, bng_ring_header* hdr, uint64_t now_ns) {
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
   for (int base = 0; base < n; base += nthreads) {
@@ -1495,12 +1554,10 @@ __global__ void antispoof_kernel(
           data + (size_t)pid * stride, in_len[pid], bindings, bmask, cfg,
           ring, hdr, now_ns, F);
     }
-    stat_inc(&stats[BNG_AS_ALLOWED], F.allowed);
-    stat_inc(&stats[BNG_AS_DROPPED], F.dropped);
-    stat_inc(&stats[BNG_AS_LOGGED], F.logged);
-    stat_inc(&stats[BNG_AS_V4_VIOLATIONS], F.v4viol);
-    stat_inc(&stats[BNG_AS_V6_VIOLATIONS], F.v6viol);
+    as_count_stats(F, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_AS, BNG_AS_NSTATS, stats);
 }
 
 /* ============================== fused uplink pipeline (the hot chain) */
@@ -1517,20 +1574,26 @@ void uplink_pipeline_kernel(bng_uplink_params P) {
   nat_tables NT{P.sessions, P.sess_mask, P.reverse, P.rev_mask, P.eim,
                 P.eim_mask, P.subctx, P.subctx_mask, P.ncfg, P.hairpin_ips,
                 P.n_hairpin, P.nat_stats, P.log_ring, P.log_hdr, P.now_ns};
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
+  /* No lane leaves an iteration early: the per-packet body is a
+   * do { } while (0) whose `break`s (bad order entry, PPPoE/ARP pass)
+   * rejoin the wave BEFORE the wave-wide stat count that ends the
+   * iteration, and every thread reaches the barrier after the loop. */
   for (int base = 0; base < P.n; base += nthreads) {
     int i = base + tid;
     dhcp_flags DF; DF.clear();
     nat_flags NF; NF.clear();
     as_flags AF{false, false, false, false, false};
     qos_flags QF{false, false, 0};
-    if (i < P.n) {
-      /* with a type-sorted order array, a wave's 64 packets share one
-       * code path — divergence between the DHCP and data pipelines no
-       * longer serializes both per wave */
+    /* with a type-sorted order array, a wave's 64 packets share one
+     * code path — divergence between the DHCP and data pipelines no
+     * longer serializes both per wave */
+    if (i < P.n) do {
       int pid = P.order ? P.order[i] : i;
-      if ((unsigned)pid >= (unsigned)P.n) continue;  /* defensive */
+      if ((unsigned)pid >= (unsigned)P.n) break;  /* defensive */
       uint8_t* p = P.data + (size_t)pid * P.stride;
       int len = P.in_len[pid];
       uint16_t ol = (uint16_t)len;
@@ -1545,7 +1608,7 @@ void uplink_pipeline_kernel(bng_uplink_params P) {
       if (et == 0x8863 || et == 0x8864 || et == 0x0806) {
         P.verdict[pid] = (uint8_t)BNG_PASS;
         P.out_len[pid] = ol;
-        continue;
+        break;
       }
       bool ip_ok = parse_pkt(c, p, len, /*want_vlan=*/true);
       bool is_dhcp = ip_ok && c.ip_off >= 0 && c.proto == 17 && c.l4_ok &&
@@ -1597,19 +1660,17 @@ void uplink_pipeline_kernel(bng_uplink_params P) {
       }
       P.verdict[pid] = (uint8_t)v;
       P.out_len[pid] = ol;
-    }
-    dhcp_commit_stats(DF, P.dhcp_stats);
-    nat_commit_stats(NF, P.nat_stats);
-    stat_inc(&P.as_stats[BNG_AS_ALLOWED], AF.allowed);
-    stat_inc(&P.as_stats[BNG_AS_DROPPED], AF.dropped);
-    stat_inc(&P.as_stats[BNG_AS_LOGGED], AF.logged);
-    stat_inc(&P.as_stats[BNG_AS_V4_VIOLATIONS], AF.v4viol);
-    stat_inc(&P.as_stats[BNG_AS_V6_VIOLATIONS], AF.v6viol);
-    stat_inc(&P.qos_stats[BNG_QS_PKT_PASSED], QF.passed);
-    stat_inc(&P.qos_stats[BNG_QS_PKT_DROPPED], QF.dropped);
-    stat_add(&P.qos_stats[BNG_QS_BYTES_PASSED], QF.bytes, QF.passed);
-    stat_add(&P.qos_stats[BNG_QS_BYTES_DROPPED], QF.bytes, QF.dropped);
+    } while (0);
+    dhcp_count_stats(DF, sb);
+    nat_count_stats(NF, sb);
+    as_count_stats(AF, sb);
+    qos_count_stats(QF, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_DHCP, BNG_DHCP_NSTATS, P.dhcp_stats);
+  sb_commit(sb, SB_NAT, BNG_NAT_NSTATS, P.nat_stats);
+  sb_commit(sb, SB_AS, BNG_AS_NSTATS, P.as_stats);
+  sb_commit(sb, SB_QOS, BNG_QOS_NSTATS, P.qos_stats);
 }
 
 /* fused downlink pipeline: internet -> subscriber return path.
@@ -1623,6 +1684,8 @@ void downlink_pipeline_kernel(bng_uplink_params P) {
   nat_tables NT{P.sessions, P.sess_mask, P.reverse, P.rev_mask, P.eim,
                 P.eim_mask, P.subctx, P.subctx_mask, P.ncfg, P.hairpin_ips,
                 P.n_hairpin, P.nat_stats, P.log_ring, P.log_hdr, P.now_ns};
+  __shared__ unsigned long long sb[SB_N];
+  sb_zero(sb, SB_N);
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int nthreads = gridDim.x * blockDim.x;
   for (int base = 0; base < P.n; base += nthreads) {
@@ -1648,12 +1711,12 @@ void downlink_pipeline_kernel(bng_uplink_params P) {
       P.verdict[pid] = (uint8_t)v;
       P.out_len[pid] = (uint16_t)len;
     }
-    nat_commit_stats(NF, P.nat_stats);
-    stat_inc(&P.qos_stats[BNG_QS_PKT_PASSED], QF.passed);
-    stat_inc(&P.qos_stats[BNG_QS_PKT_DROPPED], QF.dropped);
-    stat_add(&P.qos_stats[BNG_QS_BYTES_PASSED], QF.bytes, QF.passed);
-    stat_add(&P.qos_stats[BNG_QS_BYTES_DROPPED], QF.bytes, QF.dropped);
+    nat_count_stats(NF, sb);
+    qos_count_stats(QF, sb);
   }
+  __syncthreads();
+  sb_commit(sb, SB_NAT, BNG_NAT_NSTATS, P.nat_stats);
+  sb_commit(sb, SB_QOS, BNG_QOS_NSTATS, P.qos_stats);
 }
 
 /* classify packets for type-sorting: 1 = DHCP (UDP dst 67), 0 = other */
@@ -2050,13 +2113,34 @@ __global__ void shard_owner_kernel(const uint8_t* __restrict__ data,
 
 /* ============================= extern "C" launchers for the extension */
 
+/* Grid cap of the six batched packet kernels (grid-stride above it).
+ * Stats commit once per block, so fewer, longer-lived blocks mean fewer
+ * global atomics.  512 = two co-resident blocks on each of the 256 CUs:
+ * a 1M-packet batch is eight even iterations with no tail.  Picked by a
+ * sweep on the 1M-packet headline, where it beat every cap from 256 to
+ * 4096 (profiles/STATS_ATOMICS.md).  bng_set_pkt_grid_cap() overrides it
+ * for A/B runs and lets tests force several loop iterations at tiny n; a
+ * captured graph keeps the grid it was captured with. */
+#define BNG_PKT_GRID_CAP_DEFAULT 512
+static int g_pkt_grid_cap = BNG_PKT_GRID_CAP_DEFAULT;
+
 static inline int pkt_grid(int n) {
   int blocks = (n + 255) / 256;
-  /* memory-bound grid cap per CDNA4 guide G11: ~2048 blocks + grid-stride */
+  return blocks < g_pkt_grid_cap ? blocks : g_pkt_grid_cap;
+}
+
+/* classify / shard-owner helpers keep their own fixed cap */
+static inline int aux_grid(int n) {
+  int blocks = (n + 255) / 256;
   return blocks < 4096 ? blocks : 4096;
 }
 
 extern "C" {
+
+void bng_set_pkt_grid_cap(int blocks) {
+  g_pkt_grid_cap = blocks > 0 ? blocks : BNG_PKT_GRID_CAP_DEFAULT;
+}
+int bng_get_pkt_grid_cap(void) { return g_pkt_grid_cap; }
 
 void bng_launch_dhcp(void* data, const void* in_len, void* out_len,
                      void* verdict, int n, int stride,
@@ -2139,7 +2223,7 @@ void bng_launch_downlink(bng_uplink_params* P, hipStream_t s) {
 
 void bng_launch_pkt_class(const void* data, const void* in_len, void* cls,
                           int n, int stride, hipStream_t s) {
-  hipLaunchKernelGGL(pkt_class_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+  hipLaunchKernelGGL(pkt_class_kernel, dim3(aux_grid(n)), dim3(256), 0, s,
       (const uint8_t*)data, (const uint16_t*)in_len, (uint8_t*)cls, n,
       stride);
 }
@@ -2204,7 +2288,7 @@ void bng_launch_nat_sweep(void* sessions, uint32_t n_slots, void* reverse,
 void bng_launch_shard_owner(const void* data, const void* in_len,
                             void* owner, int n, int stride, int n_shards,
                             hipStream_t s) {
-  hipLaunchKernelGGL(shard_owner_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+  hipLaunchKernelGGL(shard_owner_kernel, dim3(aux_grid(n)), dim3(256), 0, s,
       (const uint8_t*)data, (const uint16_t*)in_len, (int32_t*)owner, n,
       stride, n_shards);
 }
