@@ -752,6 +752,11 @@ class BNG:
                 self.qos.apply_policy(sess.ip, sess.policy_name)
                 if getattr(self, "nat", None):
                     self.nat.allocate_nat(sess.ip, sess.username)
+                # session-data fast path: decap on uplink, encap on
+                # downlink, keyed by session id / subscriber address
+                self.launcher.add_pppoe_session(
+                    sess.session_id, sess.client_mac, sess.ip,
+                    mru=sess.peer_mru)
                 if getattr(self, "ha", None):
                     from ..ha.protocol import SessionState
                     self.ha.publish_add(SessionState(
@@ -762,6 +767,7 @@ class BNG:
                         policy_name=sess.policy_name))
 
             def _ppp_close(sess):
+                self.launcher.remove_pppoe_session(sess.session_id)
                 self.antispoof.remove_binding(sess.client_mac)
                 self.qos.remove_policy(sess.ip)
                 if getattr(self, "nat", None):

@@ -102,6 +102,25 @@ AS_NSTATS = 6
 AS_STAT_NAMES = ["packets_allowed", "packets_dropped", "packets_logged",
                  "ipv4_violations", "ipv6_violations", "unknown_mac"]
 
+# PPPoE session-data fast path: counters and per-packet state codes
+PS_DECAP_OK, PS_DECAP_CTRL, PS_DECAP_UNKNOWN_SESSION, PS_DECAP_MAC_MISMATCH, \
+    PS_DECAP_MALFORMED, PS_ENCAP_OK, PS_ENCAP_TOO_BIG, PS_ENCAP_NO_ROOM = \
+    range(8)
+PPPOE_NSTATS = 8
+PPPOE_STAT_NAMES = ["decap_ok", "decap_ctrl", "decap_unknown_session",
+                    "decap_mac_mismatch", "decap_malformed",
+                    "encap_ok", "encap_too_big", "encap_no_room"]
+PPPOE_NONE, PPPOE_DECAP, PPPOE_CTRL, PPPOE_REJECT, PPPOE_ENCAP, \
+    PPPOE_TOO_BIG, PPPOE_NO_ROOM = range(7)
+PPPOE_MAX_SESSIONS = 65536
+PPPOE_MAC_MASK = (1 << 48) - 1
+PPPOE_VALID = 1 << 63
+
+
+def pppoe_ip_key(ip: int) -> int:
+    """by-IP table key; bit 32 keeps it clear of EMPTY for any address."""
+    return (1 << 32) | (ip & 0xFFFFFFFF)
+
 
 class SubEntry(C.Structure):
     _fields_ = [("key", C.c_uint64), ("pool_id", C.c_uint32),
@@ -258,6 +277,17 @@ class SvcCtrl(C.Structure):
                 ("_pad", C.c_uint8 * 12)]
 
 
+class PppoeSess(C.Structure):
+    """PPPoE fast-path session entry, direct-indexed by session id."""
+    _fields_ = [("mac_valid", C.c_uint64), ("ip", C.c_uint32),
+                ("mru", C.c_uint16), ("session_id", C.c_uint16)]
+
+
+class PppoeIp(C.Structure):
+    """Subscriber IP -> (session id, client MAC) for the downlink encap."""
+    _fields_ = [("key", C.c_uint64), ("sid_mac", C.c_uint64)]
+
+
 EXPECTED_SIZES = {
     "bng_sub_entry": (SubEntry, 32),
     "bng_ip_pool": (IpPool, 28),
@@ -276,6 +306,8 @@ EXPECTED_SIZES = {
     "bng_ring_header": (RingHeader, 16),
     "bng_svc_ctrl": (SvcCtrl, 64),
     "bng_sess_export": (SessExport, 48),
+    "bng_pppoe_sess": (PppoeSess, 16),
+    "bng_pppoe_ip": (PppoeIp, 16),
 }
 
 

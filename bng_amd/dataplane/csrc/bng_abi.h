@@ -332,6 +332,49 @@ typedef struct bng_spoof_event {  /* ref spoof_event antispoof.c:46-55 */
   uint8_t  allowed_ipv6[16];
 } bng_spoof_event;  /* 56 B */
 
+/* ---------------------------------------------- PPPoE session-data path */
+/* Per-session entry of the PPPoE fast path, a flat array direct-indexed
+ * by the 16-bit PPPoE session id (65536 entries, 1 MiB: no hash, no
+ * probe).  One 16-B load serves a packet.  No reference analog — the
+ * reference terminates PPPoE entirely in user space. */
+#define BNG_PPPOE_MAX_SESSIONS 65536
+#define BNG_PPPOE_MAC_MASK     0x0000FFFFFFFFFFFFULL
+#define BNG_PPPOE_VALID        (1ULL << 63)
+
+typedef struct bng_pppoe_sess {
+  uint64_t mac_valid;   /* bits 47:0 client MAC (as mac_to_u64), bit 63 valid */
+  uint32_t ip;          /* subscriber IPv4, host int of the BE field        */
+  uint16_t mru;         /* peer MRU: largest IP packet the client accepts   */
+  uint16_t session_id;  /* == the entry's index; the upsert batch's key     */
+} bng_pppoe_sess;  /* 16 B */
+
+/* Subscriber IP -> session, for the downlink encap: open-addressing table
+ * with the usual EMPTY / TOMBSTONE keys and BNG_MAX_PROBE bound. */
+#define BNG_PPPOE_IP_KEY(ip) ((1ULL << 32) | (uint64_t)(uint32_t)(ip))
+
+typedef struct bng_pppoe_ip {
+  uint64_t key;         /* BNG_PPPOE_IP_KEY(ip); 0 empty, ~0 tombstone      */
+  uint64_t sid_mac;     /* bits 63:48 session id, bits 47:0 client MAC      */
+} bng_pppoe_ip;  /* 16 B */
+
+enum bng_pppoe_stat {
+  BNG_PS_DECAP_OK = 0, BNG_PS_DECAP_CTRL, BNG_PS_DECAP_UNKNOWN_SESSION,
+  BNG_PS_DECAP_MAC_MISMATCH, BNG_PS_DECAP_MALFORMED,
+  BNG_PS_ENCAP_OK, BNG_PS_ENCAP_TOO_BIG, BNG_PS_ENCAP_NO_ROOM,
+  BNG_PPPOE_NSTATS
+};
+
+/* per-packet state written by the decap / encap kernels */
+enum bng_pppoe_state {
+  BNG_PPPOE_NONE = 0,    /* not a PPPoE session frame / no session: untouched */
+  BNG_PPPOE_DECAP = 1,   /* uplink: header removed, now an IPoE frame         */
+  BNG_PPPOE_CTRL = 2,    /* uplink: PPP control protocol, for the host server */
+  BNG_PPPOE_REJECT = 3,  /* uplink: malformed / unknown session / wrong MAC   */
+  BNG_PPPOE_ENCAP = 4,   /* downlink: header added                            */
+  BNG_PPPOE_TOO_BIG = 5, /* downlink: exceeds the peer MRU, verdict -> PASS   */
+  BNG_PPPOE_NO_ROOM = 6, /* downlink: row too short for +8 B, verdict -> PASS */
+};
+
 /* ----------------------------------------------------------- ring header */
 /* Device->host ordered log ring: device atomically bumps widx; host reads
  * records [ridx, widx) after a stream-ordered copy, then advances ridx.

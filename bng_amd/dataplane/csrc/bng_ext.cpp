@@ -52,6 +52,15 @@ void bng_launch_nat_sweep(void*, uint32_t, void*, uint32_t, void*, uint32_t,
                           void*, hipStream_t);
 void bng_launch_shard_owner(const void*, const void*, void*, int, int, int,
                             hipStream_t);
+void bng_launch_pppoe_decap(void*, void*, void*, int, int, const void*, void*,
+                            hipStream_t);
+void bng_launch_pppoe_encap(void*, void*, void*, void*, int, int, const void*,
+                            uint32_t, const void*, const void*, void*,
+                            hipStream_t);
+void bng_launch_pppoe_sess_upsert(void*, void*, uint32_t, const void*, int,
+                                  void*, hipStream_t);
+void bng_launch_pppoe_sess_delete(void*, void*, uint32_t, const void*, int,
+                                  hipStream_t);
 void bng_set_pkt_grid_cap(int);
 int bng_get_pkt_grid_cap(void);
 void bng_launch_dhcp_service(void*, void*, const void*, void*, void*, void*,
@@ -368,6 +377,103 @@ void shard_owner(torch::Tensor data, torch::Tensor in_len,
                          (int)data.size(1), (int)n_shards, cur_stream());
 }
 
+/* PPPoE session-data fast path.  Both packet kernels move 16-B words
+ * inside a row, so the batch must be 16-B aligned with a stride that is a
+ * multiple of 16 (every batch the launcher and the pump build is). */
+void check_pppoe_batch(const torch::Tensor& data, const torch::Tensor& in_len,
+                       const torch::Tensor& sess) {
+  check_dev(data, "data"); check_dev(in_len, "in_len");
+  check_dev(sess, "pppoe_sess");
+  TORCH_CHECK(data.dim() == 2 && data.element_size() == 1,
+              "data must be [n, stride] bytes");
+  TORCH_CHECK(data.size(0) == in_len.numel() && in_len.element_size() == 2,
+              "in_len must hold one 16-bit length per row");
+  TORCH_CHECK(data.size(1) >= 64 && data.size(1) % 16 == 0 &&
+              data.size(1) <= 65535,
+              "PPPoE fast path needs a stride that is a multiple of 16, "
+              "64..65535");
+  TORCH_CHECK(((uintptr_t)data.data_ptr() & 15) == 0,
+              "PPPoE fast path needs a 16-byte aligned batch");
+  TORCH_CHECK((size_t)sess.numel() * sess.element_size() ==
+              (size_t)BNG_PPPOE_MAX_SESSIONS * sizeof(bng_pppoe_sess),
+              "pppoe_sess must hold 65536 entries");
+}
+
+void pppoe_decap(torch::Tensor data, torch::Tensor in_len,
+                 torch::Tensor state, torch::Tensor sess,
+                 torch::Tensor stats) {
+  check_pppoe_batch(data, in_len, sess);
+  check_dev(state, "state"); check_dev(stats, "stats");
+  TORCH_CHECK(state.numel() == in_len.numel() && state.element_size() == 1,
+              "state must hold one byte per row");
+  TORCH_CHECK(stats.numel() * stats.element_size() >=
+              (long)(BNG_PPPOE_NSTATS * sizeof(uint64_t)), "stats too small");
+  int n = (int)in_len.numel();
+  if (n == 0) return;
+  bng_launch_pppoe_decap(data.data_ptr(), in_len.data_ptr(),
+                         state.data_ptr(), n, (int)data.size(1),
+                         sess.data_ptr(), stats.data_ptr(), cur_stream());
+}
+
+void pppoe_encap(torch::Tensor data, torch::Tensor in_len,
+                 torch::Tensor verdict, torch::Tensor state,
+                 torch::Tensor by_ip, torch::Tensor sess,
+                 torch::Tensor scfg, torch::Tensor stats) {
+  check_pppoe_batch(data, in_len, sess);
+  check_dev(verdict, "verdict"); check_dev(state, "state");
+  check_dev(by_ip, "pppoe_by_ip"); check_dev(scfg, "scfg");
+  check_dev(stats, "stats");
+  TORCH_CHECK(state.numel() == in_len.numel() && state.element_size() == 1 &&
+              verdict.numel() == in_len.numel() &&
+              verdict.element_size() == 1,
+              "verdict and state must hold one byte per row");
+  TORCH_CHECK(stats.numel() * stats.element_size() >=
+              (long)(BNG_PPPOE_NSTATS * sizeof(uint64_t)), "stats too small");
+  TORCH_CHECK(scfg.numel() * scfg.element_size() >=
+              (long)sizeof(bng_server_config), "scfg too small");
+  int n = (int)in_len.numel();
+  if (n == 0) return;
+  bng_launch_pppoe_encap(
+      data.data_ptr(), in_len.data_ptr(), verdict.data_ptr(),
+      state.data_ptr(), n, (int)data.size(1), by_ip.data_ptr(),
+      table_mask(by_ip, sizeof(bng_pppoe_ip), "pppoe_by_ip"),
+      sess.data_ptr(), scfg.data_ptr(), stats.data_ptr(), cur_stream());
+}
+
+void pppoe_sess_upsert(torch::Tensor sess, torch::Tensor by_ip,
+                       torch::Tensor batch, torch::Tensor rc) {
+  check_dev(sess, "pppoe_sess"); check_dev(by_ip, "pppoe_by_ip");
+  check_dev(batch, "batch"); check_dev(rc, "rc");
+  TORCH_CHECK((size_t)sess.numel() * sess.element_size() ==
+              (size_t)BNG_PPPOE_MAX_SESSIONS * sizeof(bng_pppoe_sess),
+              "pppoe_sess must hold 65536 entries");
+  int n = (int)(batch.numel() * batch.element_size() /
+                sizeof(bng_pppoe_sess));
+  TORCH_CHECK(rc.numel() >= n && rc.element_size() == 4,
+              "rc must hold one int32 per record");
+  if (n == 0) return;
+  bng_launch_pppoe_sess_upsert(
+      sess.data_ptr(), by_ip.data_ptr(),
+      table_mask(by_ip, sizeof(bng_pppoe_ip), "pppoe_by_ip"),
+      batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+}
+
+void pppoe_sess_delete(torch::Tensor sess, torch::Tensor by_ip,
+                       torch::Tensor sids) {
+  check_dev(sess, "pppoe_sess"); check_dev(by_ip, "pppoe_by_ip");
+  check_dev(sids, "sids");
+  TORCH_CHECK((size_t)sess.numel() * sess.element_size() ==
+              (size_t)BNG_PPPOE_MAX_SESSIONS * sizeof(bng_pppoe_sess),
+              "pppoe_sess must hold 65536 entries");
+  TORCH_CHECK(sids.element_size() == 4, "sids must be int32");
+  int n = (int)sids.numel();
+  if (n == 0) return;
+  bng_launch_pppoe_sess_delete(
+      sess.data_ptr(), by_ip.data_ptr(),
+      table_mask(by_ip, sizeof(bng_pppoe_ip), "pppoe_by_ip"),
+      sids.data_ptr(), n, cur_stream());
+}
+
 /* Fine-grained-coherent pinned host memory for the persistent-service
  * doorbell/rings.  torch's pin_memory allocates COARSE-grained host
  * memory on ROCm: a running kernel caches it and never observes host
@@ -459,6 +565,7 @@ py::dict layout_report() {
   SZ(bng_nat_log_entry); SZ(bng_qos_bucket); SZ(bng_binding_entry);
   SZ(bng_antispoof_config); SZ(bng_spoof_event); SZ(bng_ring_header);
   SZ(bng_svc_ctrl); SZ(bng_sess_export);
+  SZ(bng_pppoe_sess); SZ(bng_pppoe_ip);
 #undef SZ
   py::dict off;
   off["sub_entry.lease_expiry"] = offsetof(bng_sub_entry, lease_expiry);
@@ -477,6 +584,10 @@ py::dict layout_report() {
   off["antispoof_config.allowed_lo"] =
       offsetof(bng_antispoof_config, allowed_lo);
   off["spoof_event.spoofed_ip"] = offsetof(bng_spoof_event, spoofed_ip);
+  off["pppoe_sess.ip"] = offsetof(bng_pppoe_sess, ip);
+  off["pppoe_sess.mru"] = offsetof(bng_pppoe_sess, mru);
+  off["pppoe_sess.session_id"] = offsetof(bng_pppoe_sess, session_id);
+  off["pppoe_ip.sid_mac"] = offsetof(bng_pppoe_ip, sid_mac);
   d["offsets"] = off;
   return d;
 }
@@ -526,6 +637,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qos_upsert", &qos_upsert);
   m.def("binding_upsert", &binding_upsert);
   m.def("binding_delete", &binding_delete);
+  m.def("pppoe_decap", &pppoe_decap);
+  m.def("pppoe_encap", &pppoe_encap);
+  m.def("pppoe_sess_upsert", &pppoe_sess_upsert);
+  m.def("pppoe_sess_delete", &pppoe_sess_delete);
   m.def("nat_sweep", &nat_sweep);
   m.def("shard_owner", &shard_owner);
   m.def("dhcp_service_start", &dhcp_service_start);

@@ -2111,6 +2111,285 @@ __global__ void shard_owner_kernel(const uint8_t* __restrict__ data,
   }
 }
 
+/* ============================== PPPoE session-data pre-pass / post-pass */
+/* PPPoE subscribers reach the fused pipelines through two small kernels
+ * of their own instead of a branch inside them: the uplink kernel sits at
+ * its 96-VGPR cap and its register-window parse wants the IPv4 header at
+ * byte 14 of a 16-B-aligned row, where a PPPoE session frame has it at
+ * byte 22.  pppoe_decap_kernel removes the 8 B of PPPoE + PPP header
+ * before the uplink kernel runs, pppoe_encap_kernel re-adds them after the
+ * downlink kernel.  Neither is launched while no session is provisioned.
+ *
+ * Rows are 16-B aligned (the extension checks stride % 16 and the base
+ * pointer), so both shifts move 16-B words: the 8-B shift makes every
+ * destination word the high half of one source word plus the low half of
+ * the next, carried in registers.  No load or store leaves the row. */
+
+/* 16 B at byte offset `off` of a row, or zeros when the word would cross
+ * the end of the row (those bytes are past the frame, never needed) */
+BNG_DEV uint4 row_ld16(const uint8_t* p, int off, int stride) {
+  if (off + 16 > stride) return make_uint4(0, 0, 0, 0);
+  return *(const uint4*)(p + off);
+}
+
+BNG_DEV uint32_t bswap16(uint32_t v) {
+  return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu);
+}
+
+struct pppoe_flags {
+  bool dec_ok, ctrl, unknown, mac_bad, malformed, enc_ok, too_big, no_room;
+};
+
+BNG_DEV void pppoe_count_stats(const pppoe_flags& F, unsigned long long* sb) {
+  sb_fold(sb, BNG_PS_DECAP_OK, wave_count(F.dec_ok));
+  sb_fold(sb, BNG_PS_DECAP_CTRL, wave_count(F.ctrl));
+  sb_fold(sb, BNG_PS_DECAP_UNKNOWN_SESSION, wave_count(F.unknown));
+  sb_fold(sb, BNG_PS_DECAP_MAC_MISMATCH, wave_count(F.mac_bad));
+  sb_fold(sb, BNG_PS_DECAP_MALFORMED, wave_count(F.malformed));
+  sb_fold(sb, BNG_PS_ENCAP_OK, wave_count(F.enc_ok));
+  sb_fold(sb, BNG_PS_ENCAP_TOO_BIG, wave_count(F.too_big));
+  sb_fold(sb, BNG_PS_ENCAP_NO_ROOM, wave_count(F.no_room));
+}
+
+/* Uplink pre-pass: a 0x8864 frame carrying PPP IPv4 from a provisioned
+ * session becomes the untagged IPoE frame with the same IP packet. */
+__global__ __launch_bounds__(256)
+void pppoe_decap_kernel(uint8_t* data, uint16_t* in_len,
+                        uint8_t* __restrict__ state, int n, int stride,
+                        const bng_pppoe_sess* __restrict__ sess,
+                        unsigned long long* stats) {
+  __shared__ unsigned long long sb[BNG_PPPOE_NSTATS];
+  sb_zero(sb, BNG_PPPOE_NSTATS);
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int pid = base + tid;
+    pppoe_flags F{false, false, false, false, false, false, false, false};
+    if (pid < n) do {
+      uint8_t* p = data + (size_t)pid * stride;
+      int len = in_len[pid];
+      if (len > stride) len = stride;      /* a row holds no more */
+      uint4 h0 = *(const uint4*)p;         /* bytes 0..15  */
+      uint8_t st = BNG_PPPOE_NONE;
+      if (len < 14 || (h0.w & 0xFFFFu) != 0x6488u) {   /* 88 64 */
+        state[pid] = st;
+        break;
+      }
+      uint4 h1 = *(const uint4*)(p + 16);  /* bytes 16..31 */
+      int plen = (int)bswap16(h1.x >> 16);
+      if (len < 22 || (h0.w >> 16) != 0x0011u ||       /* ver/type, code */
+          plen < 2 || 20 + plen > len) {
+        F.malformed = true; st = BNG_PPPOE_REJECT;
+      } else if ((h1.y & 0xFFFFu) != 0x2100u) {        /* not PPP IPv4 */
+        F.ctrl = true; st = BNG_PPPOE_CTRL;
+      } else {
+        uint32_t sid = bswap16(h1.x & 0xFFFFu);
+        uint4 e = ld_probe16(&sess[sid]);
+        uint64_t mv = ((uint64_t)e.y << 32) | e.x;
+        uint64_t mac =
+            ((uint64_t)(__builtin_bswap32(h0.y) & 0xFFFFu) << 32) |
+            __builtin_bswap32(h0.z);
+        if (!(mv & BNG_PPPOE_VALID)) {
+          F.unknown = true; st = BNG_PPPOE_REJECT;
+        } else if ((mv & BNG_PPPOE_MAC_MASK) != mac) {
+          F.mac_bad = true; st = BNG_PPPOE_REJECT;
+        } else if (plen - 2 < 20) {
+          F.malformed = true; st = BNG_PPPOE_REJECT;
+        } else {
+          F.dec_ok = true; st = BNG_PPPOE_DECAP;
+          int nlen = 12 + plen;            /* <= len - 8 <= stride - 8 */
+          /* new dword 12: ethertype 08 00 + old bytes 22..23 */
+          *(uint32_t*)(p + 12) = 0x0008u | (h1.y & 0xFFFF0000u);
+          /* new 16-B word at d = old bytes d+8 .. d+23 */
+          uint32_t c0 = h1.z, c1 = h1.w;   /* old bytes 24..31 */
+          for (int d = 16; d < nlen; d += 16) {
+            uint4 v = row_ld16(p, d + 16, stride);
+            *(uint4*)(p + d) = make_uint4(c0, c1, v.x, v.y);
+            c0 = v.z; c1 = v.w;
+          }
+          in_len[pid] = (uint16_t)nlen;
+        }
+      }
+      state[pid] = st;
+    } while (0);
+    pppoe_count_stats(F, sb);
+  }
+  __syncthreads();
+  sb_commit(sb, 0, BNG_PPPOE_NSTATS, stats);
+}
+
+/* Downlink post-pass: a forwarded IPv4 frame whose (DNAT-ed) destination
+ * belongs to a PPPoE session gets the session header back. */
+__global__ __launch_bounds__(256)
+void pppoe_encap_kernel(uint8_t* data, uint16_t* in_len, uint8_t* verdict,
+                        uint8_t* __restrict__ state, int n, int stride,
+                        const bng_pppoe_ip* __restrict__ by_ip,
+                        uint32_t ip_mask,
+                        const bng_pppoe_sess* __restrict__ sess,
+                        const bng_server_config* __restrict__ scfg,
+                        unsigned long long* stats) {
+  __shared__ unsigned long long sb[BNG_PPPOE_NSTATS];
+  sb_zero(sb, BNG_PPPOE_NSTATS);
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int pid = base + tid;
+    pppoe_flags F{false, false, false, false, false, false, false, false};
+    if (pid < n) do {
+      uint8_t* p = data + (size_t)pid * stride;
+      int len = in_len[pid];
+      uint8_t st = BNG_PPPOE_NONE;
+      state[pid] = st;
+      if (verdict[pid] != BNG_FWD || len < 34 || len > stride) break;
+      uint4 h0 = *(const uint4*)p;                     /* bytes 0..15 */
+      if ((h0.w & 0xFFFFu) != 0x0008u) break;          /* 08 00 */
+      uint4 v1 = *(const uint4*)(p + 16);              /* bytes 16..31 */
+      uint4 v2 = row_ld16(p, 32, stride);              /* bytes 32..47 */
+      /* destination address, bytes 30..33 */
+      uint32_t daddr = __builtin_bswap32((v1.w >> 16) | (v2.x << 16));
+      uint64_t key = BNG_PPPOE_IP_KEY(daddr);
+      uint32_t slot = (uint32_t)bng_mix64(key) & ip_mask;
+      uint64_t sm = 0;
+      bool hit = false;
+      for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+        uint4 e = ld_probe16(&by_ip[(slot + i) & ip_mask]);
+        uint64_t k = ((uint64_t)e.y << 32) | e.x;
+        if (k == key) { sm = ((uint64_t)e.w << 32) | e.z; hit = true; break; }
+        if (k == BNG_KEY_EMPTY) break;
+      }
+      if (!hit) break;
+      uint32_t sid = (uint32_t)(sm >> 48);
+      uint4 se = ld_probe16(&sess[sid]);
+      if (!(se.y & 0x80000000u)) break;                /* session gone */
+      int mru = (int)(se.w & 0xFFFFu);
+      if (len - 14 > mru) {
+        F.too_big = true; st = BNG_PPPOE_TOO_BIG;
+        verdict[pid] = (uint8_t)BNG_PASS;
+      } else if (len + 8 > stride) {
+        F.no_room = true; st = BNG_PPPOE_NO_ROOM;
+        verdict[pid] = (uint8_t)BNG_PASS;
+      } else {
+        F.enc_ok = true; st = BNG_PPPOE_ENCAP;
+        /* new 16-B word at d = old bytes d-8 .. d+7, highest word first:
+         * each store lands on a source word that is already in registers */
+        int top = (len + 7) & ~15;         /* last word with a frame byte */
+        uint4 hi = row_ld16(p, top, stride);
+        for (int d = top; d >= 32; d -= 16) {
+          uint4 lo = *(const uint4*)(p + d - 16);
+          *(uint4*)(p + d) = make_uint4(lo.z, lo.w, hi.x, hi.y);
+          hi = lo;
+        }
+        /* hi = old bytes 16..31.  Word 16: sid, plen, 00 21, old 14..15,
+         * then old bytes 16..23 */
+        uint32_t plen = (uint32_t)(len - 14 + 2);
+        *(uint4*)(p + 16) = make_uint4(
+            bswap16(sid) | (bswap16(plen) << 16),
+            0x2100u | (h0.w & 0xFFFF0000u), hi.x, hi.y);
+        /* word 0: client MAC, server MAC, 88 64, 11 00 */
+        uint32_t mhi = (uint32_t)(sm >> 32) & 0xFFFFu;  /* MAC bytes 0..1 */
+        uint32_t mlo = (uint32_t)sm;                    /* MAC bytes 2..5 */
+        uint32_t cw0 = bswap16(mhi) | (bswap16(mlo >> 16) << 16);
+        uint32_t cw1 = bswap16(mlo & 0xFFFFu);
+        const uint8_t* sv = scfg->server_mac;
+        cw1 |= ((uint32_t)sv[0] << 16) | ((uint32_t)sv[1] << 24);
+        uint32_t cw2 = (uint32_t)sv[2] | ((uint32_t)sv[3] << 8) |
+                       ((uint32_t)sv[4] << 16) | ((uint32_t)sv[5] << 24);
+        *(uint4*)p = make_uint4(cw0, cw1, cw2, 0x00116488u);
+        in_len[pid] = (uint16_t)(len + 8);
+      }
+      state[pid] = st;
+    } while (0);
+    pppoe_count_stats(F, sb);
+  }
+  __syncthreads();
+  sb_commit(sb, 0, BNG_PPPOE_NSTATS, stats);
+}
+
+/* Stream-ordered session CRUD, one thread per batch record.  A batch must
+ * not name the same session id or the same IP twice. */
+BNG_DEV void pppoe_ip_remove(bng_pppoe_ip* t, uint32_t mask, uint32_t ip,
+                             uint32_t sid) {
+  uint64_t key = BNG_PPPOE_IP_KEY(ip);
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
+    bng_pppoe_ip* s = &t[(slot + k) & mask];
+    uint64_t cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) {
+      /* only the owner removes it: the address may already belong to a
+       * newer session */
+      if ((uint32_t)(s->sid_mac >> 48) == sid)
+        __hip_atomic_store(&s->key, BNG_KEY_TOMBSTONE, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    if (cur == BNG_KEY_EMPTY) return;
+  }
+}
+
+__global__ void pppoe_sess_upsert_kernel(bng_pppoe_sess* sess,
+                                         bng_pppoe_ip* t, uint32_t mask,
+                                         const bng_pppoe_sess* batch, int n,
+                                         int* rc) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bng_pppoe_sess e = batch[i];
+  uint32_t sid = e.session_id;
+  uint64_t mac = e.mac_valid & BNG_PPPOE_MAC_MASK;
+  bng_pppoe_sess old = sess[sid];
+  /* same id, other address: the stale by-IP entry must go */
+  if ((old.mac_valid & BNG_PPPOE_VALID) && old.ip != e.ip)
+    pppoe_ip_remove(t, mask, old.ip, sid);
+  uint64_t key = BNG_PPPOE_IP_KEY(e.ip);
+  uint64_t val = ((uint64_t)sid << 48) | mac;
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  int first_tomb = -1;
+  bool done = false;
+  for (int k = 0; k < BNG_MAX_PROBE && !done; ++k) {
+    bng_pppoe_ip* s = &t[(slot + k) & mask];
+    uint64_t cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) { s->sid_mac = val; done = true; break; }
+    if (cur == BNG_KEY_TOMBSTONE && first_tomb < 0)
+      first_tomb = (int)((slot + k) & mask);
+    if (cur == BNG_KEY_EMPTY) {
+      int target = first_tomb >= 0 ? first_tomb : (int)((slot + k) & mask);
+      bng_pppoe_ip* d = &t[target];
+      uint64_t expect = first_tomb >= 0 ? BNG_KEY_TOMBSTONE : BNG_KEY_EMPTY;
+      if (__hip_atomic_compare_exchange_strong(
+              &d->key, &expect, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+              __HIP_MEMORY_SCOPE_AGENT)) {
+        d->sid_mac = val; done = true; break;
+      }
+      /* raced with another upsert in this batch; retry from here */
+      first_tomb = -1;
+      continue;
+    }
+  }
+  if (!done) {
+    /* by-IP chain full: leave the session out of both tables so the two
+     * directions stay consistent */
+    sess[sid] = bng_pppoe_sess{0, 0, 0, 0};
+    if (rc) rc[i] = -1;
+    return;
+  }
+  e.mac_valid = mac | BNG_PPPOE_VALID;
+  sess[sid] = e;
+  if (rc) rc[i] = 0;
+}
+
+__global__ void pppoe_sess_delete_kernel(bng_pppoe_sess* sess,
+                                         bng_pppoe_ip* t, uint32_t mask,
+                                         const int32_t* sids, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t sid = (uint32_t)sids[i] & 0xFFFFu;
+  bng_pppoe_sess old = sess[sid];
+  if (!(old.mac_valid & BNG_PPPOE_VALID)) return;
+  pppoe_ip_remove(t, mask, old.ip, sid);
+  sess[sid] = bng_pppoe_sess{0, 0, 0, 0};
+}
+
 /* ============================= extern "C" launchers for the extension */
 
 /* Grid cap of the six batched packet kernels (grid-stride above it).
@@ -2283,6 +2562,41 @@ void bng_launch_nat_sweep(void* sessions, uint32_t n_slots, void* reverse,
       rev_mask, (bng_subctx*)subnat, subnat_mask, (bng_eim_entry*)eim,
       eim_slots, eim_to, now_ns, udp_to,
       tcp_est_to, tcp_tr_to, icmp_to, (unsigned long long*)stats);
+}
+
+void bng_launch_pppoe_decap(void* data, void* in_len, void* state, int n,
+                            int stride, const void* sess, void* stats,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(pppoe_decap_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (uint8_t*)data, (uint16_t*)in_len, (uint8_t*)state, n, stride,
+      (const bng_pppoe_sess*)sess, (unsigned long long*)stats);
+}
+
+void bng_launch_pppoe_encap(void* data, void* in_len, void* verdict,
+                            void* state, int n, int stride,
+                            const void* by_ip, uint32_t ip_mask,
+                            const void* sess, const void* scfg, void* stats,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(pppoe_encap_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (uint8_t*)data, (uint16_t*)in_len, (uint8_t*)verdict, (uint8_t*)state,
+      n, stride, (const bng_pppoe_ip*)by_ip, ip_mask,
+      (const bng_pppoe_sess*)sess, (const bng_server_config*)scfg,
+      (unsigned long long*)stats);
+}
+
+void bng_launch_pppoe_sess_upsert(void* sess, void* by_ip, uint32_t ip_mask,
+                                  const void* batch, int n, void* rc,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(pppoe_sess_upsert_kernel, dim3((n + 255) / 256),
+      dim3(256), 0, s, (bng_pppoe_sess*)sess, (bng_pppoe_ip*)by_ip, ip_mask,
+      (const bng_pppoe_sess*)batch, n, (int*)rc);
+}
+
+void bng_launch_pppoe_sess_delete(void* sess, void* by_ip, uint32_t ip_mask,
+                                  const void* sids, int n, hipStream_t s) {
+  hipLaunchKernelGGL(pppoe_sess_delete_kernel, dim3((n + 255) / 256),
+      dim3(256), 0, s, (bng_pppoe_sess*)sess, (bng_pppoe_ip*)by_ip, ip_mask,
+      (const int32_t*)sids, n);
 }
 
 void bng_launch_shard_owner(const void* data, const void* in_len,

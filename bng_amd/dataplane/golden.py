@@ -114,6 +114,13 @@ class BindingRec:
     mode: int = abi.AS_DISABLED
 
 
+@dataclass
+class PppoeSessRec:
+    mac: int                   # client MAC as u64 (abi.mac_to_u64)
+    ip: int                    # subscriber IPv4, host int of the BE field
+    mru: int = 1492
+
+
 DEFAULT_PRIVATE_RANGES = [
     # is_private_ip inline ranges, ref nat44.c:340-363
     (0x0A000000, 0xFF000000),                    # 10.0.0.0/8
@@ -156,6 +163,10 @@ class GoldenDataplane:
         self.allowed_ranges: List[Tuple[int, int]] = []
         self.as_stats = [0] * abi.AS_NSTATS
         self.spoof_events: List[dict] = []
+        # PPPoE session-data fast path
+        self.pppoe_sessions: Dict[int, PppoeSessRec] = {}   # by session id
+        self.pppoe_by_ip: Dict[int, Tuple[int, int]] = {}   # ip -> (sid, mac)
+        self.pppoe_stats = [0] * abi.PPPOE_NSTATS
 
     # ------------------------------------------------------------- helpers
     @property
@@ -658,6 +669,99 @@ class GoldenDataplane:
         self.qos_stats[abi.QS_PKT_DROPPED] += 1
         self.qos_stats[abi.QS_BYTES_DROPPED] += len(frame)
         return DROP
+
+    # ============================================== PPPoE session data
+    def pppoe_add_session(self, session_id: int, client_mac, ip: int,
+                          mru: int = 1492):
+        """Upsert; re-using a session id with another address removes the
+        stale by-IP entry (pppoe_sess_upsert_kernel)."""
+        sid = session_id & 0xFFFF
+        mac = client_mac if isinstance(client_mac, int) \
+            else abi.mac_to_u64(bytes(client_mac))
+        old = self.pppoe_sessions.get(sid)
+        if old is not None and old.ip != ip and \
+                self.pppoe_by_ip.get(old.ip, (None,))[0] == sid:
+            del self.pppoe_by_ip[old.ip]
+        self.pppoe_sessions[sid] = PppoeSessRec(mac, ip, mru)
+        self.pppoe_by_ip[ip] = (sid, mac)
+
+    def pppoe_remove_session(self, session_id: int):
+        sid = session_id & 0xFFFF
+        old = self.pppoe_sessions.pop(sid, None)
+        # only the owner removes the by-IP entry: the address may already
+        # belong to a newer session
+        if old is not None and \
+                self.pppoe_by_ip.get(old.ip, (None,))[0] == sid:
+            del self.pppoe_by_ip[old.ip]
+
+    def pppoe_decap(self, frame: bytearray) -> Tuple[int, int]:
+        """Uplink pre-pass (pppoe_decap_kernel): a 0x8864 frame carrying
+        PPP IPv4 from a provisioned session is rewritten in place into the
+        untagged IPoE frame with the same IP packet.  Returns (state,
+        new_len); bytes at and beyond new_len are unspecified."""
+        n = len(frame)
+        if n < 14 or struct.unpack_from(">H", frame, 12)[0] != 0x8864:
+            return abi.PPPOE_NONE, n
+        st = self.pppoe_stats
+        if n < 22:
+            st[abi.PS_DECAP_MALFORMED] += 1
+            return abi.PPPOE_REJECT, n
+        if frame[14] != 0x11 or frame[15] != 0x00:
+            st[abi.PS_DECAP_MALFORMED] += 1
+            return abi.PPPOE_REJECT, n
+        plen = struct.unpack_from(">H", frame, 18)[0]
+        if plen < 2 or 20 + plen > n:
+            st[abi.PS_DECAP_MALFORMED] += 1
+            return abi.PPPOE_REJECT, n
+        if struct.unpack_from(">H", frame, 20)[0] != 0x0021:
+            # LCP / auth / IPCP / IPv6: the host PPPoE server's business;
+            # checked before the session lookup because the table holds a
+            # session only from IPCP-open
+            st[abi.PS_DECAP_CTRL] += 1
+            return abi.PPPOE_CTRL, n
+        sess = self.pppoe_sessions.get(struct.unpack_from(">H", frame, 16)[0])
+        if sess is None:
+            st[abi.PS_DECAP_UNKNOWN_SESSION] += 1
+            return abi.PPPOE_REJECT, n
+        if abi.mac_to_u64(bytes(frame[6:12])) != sess.mac:
+            st[abi.PS_DECAP_MAC_MISMATCH] += 1
+            return abi.PPPOE_REJECT, n
+        if plen - 2 < 20:
+            st[abi.PS_DECAP_MALFORMED] += 1
+            return abi.PPPOE_REJECT, n
+        frame[12:14] = b"\x08\x00"
+        frame[14:12 + plen] = frame[22:20 + plen]
+        st[abi.PS_DECAP_OK] += 1
+        return abi.PPPOE_DECAP, 12 + plen      # Ethernet padding trimmed
+
+    def pppoe_encap(self, frame: bytearray, verdict: int,
+                    stride: int) -> Tuple[int, int, int]:
+        """Downlink post-pass (pppoe_encap_kernel): a forwarded IPv4 frame
+        whose (DNAT-ed) destination is a PPPoE subscriber gets the session
+        header back, in place (the bytearray grows by 8).  Returns (state,
+        verdict, new_len)."""
+        n = len(frame)
+        if verdict != FWD or n < 34 or \
+                struct.unpack_from(">H", frame, 12)[0] != ETH_P_IP:
+            return abi.PPPOE_NONE, verdict, n
+        hit = self.pppoe_by_ip.get(struct.unpack_from(">I", frame, 30)[0])
+        sess = self.pppoe_sessions.get(hit[0]) if hit is not None else None
+        if sess is None:
+            return abi.PPPOE_NONE, verdict, n
+        sid, mac = hit
+        if n - 14 > sess.mru:
+            # the host decides between fragmentation and ICMP
+            self.pppoe_stats[abi.PS_ENCAP_TOO_BIG] += 1
+            return abi.PPPOE_TOO_BIG, PASS, n
+        if n + 8 > stride:
+            self.pppoe_stats[abi.PS_ENCAP_NO_ROOM] += 1
+            return abi.PPPOE_NO_ROOM, PASS, n
+        frame[0:14] = (mac.to_bytes(6, "big") + bytes(self.server_mac) +
+                       b"\x88\x64" +
+                       struct.pack(">BBHHH", 0x11, 0x00, sid, n - 14 + 2,
+                                   0x0021))
+        self.pppoe_stats[abi.PS_ENCAP_OK] += 1
+        return abi.PPPOE_ENCAP, verdict, n + 8
 
     # ====================================================== antispoof K4
     def antispoof(self, frame: bytes) -> int:

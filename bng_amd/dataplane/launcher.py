@@ -47,7 +47,7 @@ class HipLauncher:
                  sub_log2: int = 18, sess_log2: int = 20, eim_log2: int = 19,
                  subnat_log2: int = 18, qos_log2: int = 18,
                  binding_log2: int = 18, n_pools: int = 1024,
-                 svc_cus: int = 0):
+                 svc_cus: int = 0, pppoe_log2: int = 17):
         import torch
         from .build import get_ext
         self.torch = torch
@@ -99,6 +99,17 @@ class HipLauncher:
         self.spoof_ring = z((1 << abi.SPOOF_RING_LOG2) * 56)
         self.spoof_hdr = z(16)
         self._spoof_ridx = 0
+        # PPPoE session-data fast path: sessions direct-indexed by the
+        # 16-bit session id, plus subscriber IP -> session for the downlink
+        # encap (2^17 slots: load <= 0.5 with every session id in use)
+        self.pppoe_sess = z(abi.PPPOE_MAX_SESSIONS * 16)
+        self.pppoe_by_ip = z((1 << pppoe_log2) * 16)
+        self.pppoe_stats = torch.zeros(abi.PPPOE_NSTATS, dtype=torch.int64,
+                                       device=self.device)
+        # host-side count of live sessions: while it is zero uplink() and
+        # downlink() launch exactly what they launched before PPPoE existed
+        self._pppoe_live: Dict[int, Tuple[int, int]] = {}
+        self.last_pppoe_state = None
         # host-side circuit-id collision registry (ref loader.go:519-608)
         self._circuit_ids: Dict[int, bytes] = {}
         # defaults
@@ -350,6 +361,92 @@ class HipLauncher:
                                 abi.SpoofEvent, 56, abi.SPOOF_RING_LOG2,
                                 "_spoof_ridx")
 
+    # ========================================== PPPoE session-data path
+    def add_pppoe_session(self, session_id: int, client_mac, ip: int,
+                          mru: int = 1492):
+        """Provision an opened PPPoE session (IPCP up) on the device:
+        uplink data frames of this session id + client MAC are decapsulated
+        ahead of the uplink pipeline, and downlink frames to `ip` leave
+        re-encapsulated."""
+        self.add_pppoe_sessions([(session_id, client_mac, ip, mru)])
+
+    def add_pppoe_sessions(self, sessions):
+        """Bulk form of add_pppoe_session: (session_id, client_mac, ip,
+        mru) tuples, one launch.  A batch must not repeat a session id or
+        an address."""
+        import numpy as np
+        recs = []
+        for sid, mac, ip, mru in sessions:
+            if not 0 <= sid < abi.PPPOE_MAX_SESSIONS:
+                raise ValueError(f"PPPoE session id out of range: {sid}")
+            m = mac if isinstance(mac, int) else abi.mac_to_u64(bytes(mac))
+            recs.append((m & abi.PPPOE_MAC_MASK, ip & 0xFFFFFFFF,
+                         max(0, min(int(mru), 0xFFFF)), sid))
+        if not recs:
+            return
+        arr = np.array(recs, dtype=[("mac_valid", "<u8"), ("ip", "<u4"),
+                                    ("mru", "<u2"), ("session_id", "<u2")])
+        batch = self.torch.from_numpy(arr.view(np.uint8)).to(self.device)
+        rc = self.torch.zeros(len(recs), dtype=self.torch.int32,
+                              device=self.device)
+        self.ext.pppoe_sess_upsert(self.pppoe_sess, self.pppoe_by_ip,
+                                   batch, rc)
+        # session-open is a control-plane event: pay the sync and keep the
+        # host-side count exact
+        bad = (rc != 0).cpu().numpy()
+        for (m, ip, _mru, sid), failed in zip(recs, bad):
+            if failed:
+                self._pppoe_live.pop(sid, None)
+            else:
+                self._pppoe_live[sid] = (m, ip)
+        if bad.any():
+            raise RuntimeError(
+                f"PPPoE by-IP table full: {int(bad.sum())} session(s) not "
+                "provisioned (raise pppoe_log2)")
+
+    def remove_pppoe_session(self, session_id: int):
+        import numpy as np
+        sid = session_id & 0xFFFF
+        sids = self.torch.from_numpy(
+            np.array([sid], dtype=np.int32)).to(self.device)
+        self.ext.pppoe_sess_delete(self.pppoe_sess, self.pppoe_by_ip, sids)
+        self._pppoe_live.pop(sid, None)
+
+    def clear_pppoe_sessions(self):
+        """Drop every session at once (both tables, stream-ordered)."""
+        self.pppoe_sess.zero_()
+        self.pppoe_by_ip.zero_()
+        self._pppoe_live.clear()
+
+    @property
+    def pppoe_session_count(self) -> int:
+        return len(self._pppoe_live)
+
+    def pppoe_get_stats(self) -> Dict[str, int]:
+        return dict(zip(abi.PPPOE_STAT_NAMES,
+                        self.pppoe_stats.cpu().tolist()))
+
+    def pppoe_decap(self, data, lens):
+        """Uplink pre-pass, in place: provisioned PPPoE IPv4 data frames
+        become untagged IPoE frames and `lens` shrinks by 8 (and by any
+        Ethernet padding).  Returns the per-packet state (abi.PPPOE_*)."""
+        state = self.torch.empty(lens.numel(), dtype=self.torch.uint8,
+                                 device=self.device)
+        self.ext.pppoe_decap(data, lens, state, self.pppoe_sess,
+                             self.pppoe_stats)
+        return state
+
+    def pppoe_encap(self, data, lens, verdict):
+        """Downlink post-pass, in place: forwarded IPv4 frames addressed to
+        a PPPoE subscriber get the session header back and `lens` grows by
+        8; TOO_BIG / NO_ROOM frames are left alone with verdict PASS."""
+        state = self.torch.empty(lens.numel(), dtype=self.torch.uint8,
+                                 device=self.device)
+        self.ext.pppoe_encap(data, lens, verdict, state, self.pppoe_by_ip,
+                             self.pppoe_sess, self.server_cfg,
+                             self.pppoe_stats)
+        return state
+
     # ================================================ batched processing
     def make_batch(self, frames: Sequence[bytes], stride: int = 512):
         """Pack frames into a device batch (data[n,stride], len[n])."""
@@ -419,10 +516,17 @@ class HipLauncher:
         sort_by_type=True first classifies packets on-device and feeds the
         kernel a type-sorted index order, so each wave's 64 lanes run ONE
         of the two pipelines instead of serializing both (the wave-
-        divergence fix; packet data itself is not moved)."""
+        divergence fix; packet data itself is not moved).
+
+        With PPPoE sessions provisioned, pppoe_decap() runs first (so the
+        classifier and the pipeline see IPoE frames and `lens` is updated
+        in place), frames it rejects leave with DROP, and the per-packet
+        state stays reachable as last_pppoe_state."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
+        state = self.pppoe_decap(data, lens) \
+            if self._pppoe_live and n else None
         if order is None and sort_by_type and n > 64:
             cls = self.torch.empty(n, dtype=self.torch.uint8,
                                    device=self.device)
@@ -437,10 +541,15 @@ class HipLauncher:
             self.nat_log_hdr, self.qos_egress, self.qos_stats, now,
             now_sec if now_sec is not None else now // 10**9, order=order,
             masked=self.masked_compute)
+        if state is not None:
+            verdict.masked_fill_(state == abi.PPPOE_REJECT, abi.DROP)
+            self.last_pppoe_state = state
         return verdict, out_len
 
     def downlink(self, data, lens, now_ns: Optional[int] = None):
-        """Fused NAT44 DNAT -> QoS-egress return path."""
+        """Fused NAT44 DNAT -> QoS-egress return path.  With PPPoE sessions
+        provisioned, pppoe_encap() follows: `lens` is updated in place and
+        the state stays reachable as last_pppoe_state."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
@@ -453,6 +562,8 @@ class HipLauncher:
             self.nat_log_hdr, self.qos_egress, self.qos_stats, now,
             now // 10**9, order=None, downlink=True,
             masked=self.masked_compute)
+        if self._pppoe_live and n:
+            self.last_pppoe_state = self.pppoe_encap(data, lens, verdict)
         return verdict
 
     # ------------------------------------------- HA table snapshotting
@@ -575,7 +686,8 @@ class DhcpService:
     same always-resident property, dhcp_fastpath.c:619).
 
     Latency path only — the batched dhcp_fastpath/uplink kernels remain
-    the throughput path."""
+    the throughput path.  IPoE only: the service does not run the PPPoE
+    session-data pre-pass."""
 
     # Pinned-coherent buffers are allocated ONCE per (n_slots, stride)
     # and cached for the process lifetime: hipHostMalloc/hipHostFree
@@ -857,6 +969,42 @@ class GoldenLauncher:
         out, self.dp.spoof_events = self.dp.spoof_events, []
         return out
 
+    # PPPoE session-data path (frames as list[bytearray], lens as
+    # list[int]; both updated in place like the device tensors)
+    def add_pppoe_session(self, session_id, client_mac, ip, mru=1492):
+        self.dp.pppoe_add_session(session_id, client_mac, ip, mru)
+
+    def remove_pppoe_session(self, session_id):
+        self.dp.pppoe_remove_session(session_id)
+
+    def clear_pppoe_sessions(self):
+        self.dp.pppoe_sessions.clear()
+        self.dp.pppoe_by_ip.clear()
+
+    @property
+    def pppoe_session_count(self):
+        return len(self.dp.pppoe_sessions)
+
+    def pppoe_get_stats(self):
+        return dict(zip(abi.PPPOE_STAT_NAMES, self.dp.pppoe_stats))
+
+    def pppoe_decap(self, data, lens):
+        states = []
+        for i, fb in enumerate(data):
+            del fb[lens[i]:]
+            st, lens[i] = self.dp.pppoe_decap(fb)
+            states.append(st)
+        return states
+
+    def pppoe_encap(self, data, lens, verdict, stride=512):
+        states = []
+        for i, fb in enumerate(data):
+            del fb[lens[i]:]
+            st, verdict[i], lens[i] = self.dp.pppoe_encap(fb, verdict[i],
+                                                          stride)
+            states.append(st)
+        return states
+
     # processing (frames as list[bytearray]); mirrors HipLauncher outputs
     def process_dhcp(self, frames, now_sec=None):
         if now_sec is not None:
@@ -950,7 +1098,10 @@ def make_launcher(prefer_gpu: bool = True, **kw):
 
 
 class CapturedUplink:
-    """hipGraph replay wrapper for the fused uplink pipeline."""
+    """hipGraph replay wrapper for the fused uplink pipeline.
+
+    The PPPoE session-data pre-pass is not part of the captured sequence:
+    PPPoE data frames replayed through it PASS to the host as before."""
 
     def __init__(self, launcher: HipLauncher, n: int, stride: int,
                  sort_by_type: bool):
@@ -1006,7 +1157,10 @@ class CapturedUplink:
 
 
 class CapturedDHCP:
-    """hipGraph replay wrapper for the DHCP fast path (latency path)."""
+    """hipGraph replay wrapper for the DHCP fast path (latency path).
+
+    IPoE only: DHCP carried inside PPPoE is out of scope, so the PPPoE
+    session-data pre-pass is not captured here."""
 
     def __init__(self, launcher: HipLauncher, n: int, stride: int):
         import torch

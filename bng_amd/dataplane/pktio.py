@@ -309,7 +309,10 @@ class Pump:
             self.stats["dropped"] += int(
                 len(frames) - tx.sum() - fwd.sum() - pas.sum())
             out_mask = tx | fwd
-            out_lens = np.where(tx, ol, lens_np).astype(np.uint16)[out_mask]
+            # forwarded lengths come from the device: the PPPoE pre-pass
+            # shortens the frames it decapsulates
+            lens_dev = lens.cpu().numpy().view(np.uint16)
+            out_lens = np.where(tx, ol, lens_dev).astype(np.uint16)[out_mask]
             out_data = host[out_mask]
             # PASS frames go to the slow path (few: cache misses only)
             passed = [frames[i] for i in np.nonzero(pas)[0]]
@@ -359,7 +362,21 @@ class Pump:
             # uplink kernel: DHCP frames that miss go to the slow path,
             # not down the data pipeline
             import struct as _st
+            dp = self.launcher.dp
             for fr in frames:
+                orig = fr
+                # PPPoE session-data pre-pass, as HipLauncher.uplink runs
+                # it: data frames of provisioned sessions continue below
+                # as IPoE, rejected ones are dropped, control protocols
+                # (and everything else) route as before
+                if dp.pppoe_sessions:
+                    fb = bytearray(fr)
+                    pst, L = dp.pppoe_decap(fb)
+                    if pst == abi.PPPOE_REJECT:
+                        self.stats["dropped"] += 1
+                        continue
+                    if pst == abi.PPPOE_DECAP:
+                        fr = bytes(fb[:L])
                 # PPPoE/ARP ethertypes -> slow path (see uplink
                 # kernel note; ARP for the gateway is answered there)
                 if len(fr) >= 14 and _st.unpack_from(">H", fr, 12)[0] \
@@ -378,7 +395,7 @@ class Pump:
                     continue
                 if is_dhcp and len(fr) >= 38 and fr[23] == 17 and \
                         _st.unpack_from(">H", fr, 36)[0] == 67:
-                    passed.append(fr)
+                    passed.append(orig)
                     self.stats["passed"] += 1
                     continue
                 vd = self.launcher.dp.antispoof(bytes(fr))
@@ -391,7 +408,9 @@ class Pump:
                     out_frames.append(bytes(fb))
                     self.stats["fwd"] += 1
                 elif vd == abi.PASS:
-                    passed.append(fr)
+                    # the slow path gets the frame as received, like the
+                    # GPU branch above
+                    passed.append(orig)
                     self.stats["passed"] += 1
                 else:
                     self.stats["dropped"] += 1
@@ -417,8 +436,10 @@ class Pump:
         """Core-side batch: fused NAT44 DNAT -> QoS-egress.  The
         downlink kernel rewrites frames in place and returns a verdict
         per frame (FWD toward the subscriber, DROP on shaping).  No
-        DHCP/ARP/PPPoE handling here — control traffic lives on the
-        access side."""
+        DHCP/ARP/PPPoE control handling here — control traffic lives on
+        the access side.  Frames for PPPoE subscribers leave
+        re-encapsulated (and 8 B longer); ones that exceed the peer MRU
+        or the row come back PASS for the host to fragment or refuse."""
         is_gpu = hasattr(self.launcher, "make_batch")
         out_frames: List[bytes] = []
         passed: List[bytes] = []
@@ -439,7 +460,8 @@ class Pump:
             self.stats["dropped"] += int(len(frames) - fwd.sum() - pas.sum())
             out_mask = fwd
             out_data = host[out_mask]
-            out_lens = lens_np[out_mask]
+            # lengths from the device: PPPoE encap grows frames by 8
+            out_lens = lens.cpu().numpy().view(np.uint16)[out_mask]
             passed = [frames[i] for i in np.nonzero(pas)[0]]
             if self.sink is not None:
                 if hasattr(self.sink, "send_batch_array"):
@@ -455,6 +477,9 @@ class Pump:
             vd = self.launcher.dp.nat44_ingress(fb)
             if vd == abi.FWD:
                 vd = self.launcher.dp.qos(bytes(fb), "egress")
+            if self.launcher.dp.pppoe_sessions:
+                _pst, vd, _L = self.launcher.dp.pppoe_encap(
+                    fb, vd, self.stride)
             if vd == abi.FWD:
                 out_frames.append(bytes(fb))
                 self.stats["fwd"] += 1

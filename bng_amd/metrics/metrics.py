@@ -108,6 +108,13 @@ class Metrics:
         self.pppoe_negotiations = Counter(
             "bng_pppoe_negotiations_total", "PPPoE phase outcomes",
             ["phase", "result"], registry=r)
+        # PPPoE session-data fast path (device decap / encap counters)
+        from ..dataplane.abi import PPPOE_STAT_NAMES
+        self.pppoe_fastpath = {
+            name: Gauge(f"bng_pppoe_fastpath_{name}_total",
+                        f"PPPoE fast path: {name.replace('_', ' ')} frames",
+                        registry=r)
+            for name in PPPOE_STAT_NAMES}
         self.routes_active = Gauge(
             "bng_routes_active", "installed routes", ["proto"],
             registry=r)
@@ -172,6 +179,10 @@ class Metrics:
                 self.dataplane_stat.labels("antispoof", name).set(v)
             self.antispoof_violations.set(
                 launcher.antispoof_get_stats().get("ipv4_violations", 0))
+            if hasattr(launcher, "pppoe_get_stats"):
+                for name, v in launcher.pppoe_get_stats().items():
+                    self.dataplane_stat.labels("pppoe", name).set(v)
+                    self.pppoe_fastpath[name].set(v)
         if dhcp_server is not None:
             for pool_stats in dhcp_server.pools.all_stats():
                 pid = str(pool_stats["pool_id"])
