@@ -267,6 +267,14 @@ SESS_EXPORT_DTYPE = [("src_ip", "<u4"), ("dst_ip", "<u4"),
                      ("last_seen", "<u8"), ("_pad", "<u8")]
 
 
+# bng_sub_entry as a numpy record (bulk subscriber import/export); field
+# names and offsets are SubEntry's
+SUB_ENTRY_DTYPE = [("key", "<u8"), ("pool_id", "<u4"),
+                   ("allocated_ip", "<u4"), ("lease_expiry", "<u8"),
+                   ("vlan_id", "<u2"), ("client_class", "u1"),
+                   ("flags", "u1"), ("_pad", "<u4")]
+
+
 class SvcCtrl(C.Structure):
     """Pinned-host doorbell of the persistent DHCP service kernel."""
     _fields_ = [("head", C.c_uint32), ("tail", C.c_uint32),

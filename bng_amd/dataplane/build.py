@@ -6,6 +6,7 @@ bng_amd.dataplane.build` (or __graft_entry__.build()) compiles it.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import sys
@@ -22,7 +23,8 @@ SOURCES = [
 
 
 def _sources_mtime() -> float:
-    hdrs = [os.path.join(CSRC, h) for h in ("bng_abi.h", "bng_device.h")]
+    """Newest mtime of the sources and of every header under csrc/."""
+    hdrs = glob.glob(os.path.join(CSRC, "*.h"))
     return max(os.path.getmtime(f) for f in SOURCES + hdrs)
 
 

@@ -10,64 +10,13 @@
  * test/ebpf/maps_test.go struct-ABI tests).
  */
 #include <torch/extension.h>
+#include <climits>
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
 #include "bng_abi.h"
 #include "bng_params.h"
-
-extern "C" {
-void bng_launch_dhcp(void*, const void*, void*, void*, int, int, const void*,
-                     uint32_t, const void*, uint32_t, const void*, void*,
-                     uint64_t, const void*, hipStream_t);
-void bng_launch_nat44(void*, const void*, void*, int, int, int, void*,
-                      uint32_t, void*, uint32_t, void*, uint32_t, void*,
-                      uint32_t, const void*, const void*, uint32_t, void*,
-                      void*, void*, uint64_t, hipStream_t);
-void bng_launch_qos(void*, const void*, void*, int, int, int, void*,
-                    uint32_t, void*, uint64_t, hipStream_t);
-void bng_launch_antispoof(void*, const void*, void*, int, int, const void*,
-                          uint32_t, const void*, void*, void*, void*,
-                          uint64_t, hipStream_t);
-void bng_launch_uplink(bng_uplink_params*, hipStream_t);
-void bng_launch_downlink(bng_uplink_params*, hipStream_t);
-void bng_launch_pkt_class(const void*, const void*, void*, int, int,
-                          hipStream_t);
-void bng_launch_sub_upsert(void*, uint32_t, const void*, int, void*,
-                           hipStream_t);
-void bng_launch_sub_delete(void*, uint32_t, const void*, int, hipStream_t);
-void bng_launch_sess_import(void*, uint32_t, void*, uint32_t, void*,
-                            uint32_t, const void*, int, void*, hipStream_t);
-void bng_launch_subctx_upsert(void*, uint32_t, const void*, int, uint32_t,
-                              void*, hipStream_t);
-void bng_launch_qos_upsert(void*, uint32_t, const void*, int, void*,
-                           hipStream_t);
-void bng_launch_binding_upsert(void*, uint32_t, const void*, int, void*,
-                               hipStream_t);
-void bng_launch_binding_delete(void*, uint32_t, const void*, int,
-                               hipStream_t);
-void bng_launch_nat_sweep(void*, uint32_t, void*, uint32_t, void*, uint32_t,
-                          void*, uint32_t, uint64_t,
-                          uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                          void*, hipStream_t);
-void bng_launch_shard_owner(const void*, const void*, void*, int, int, int,
-                            hipStream_t);
-void bng_launch_pppoe_decap(void*, void*, void*, int, int, const void*, void*,
-                            hipStream_t);
-void bng_launch_pppoe_encap(void*, void*, void*, void*, int, int, const void*,
-                            uint32_t, const void*, const void*, void*,
-                            hipStream_t);
-void bng_launch_pppoe_sess_upsert(void*, void*, uint32_t, const void*, int,
-                                  void*, hipStream_t);
-void bng_launch_pppoe_sess_delete(void*, void*, uint32_t, const void*, int,
-                                  hipStream_t);
-void bng_set_pkt_grid_cap(int);
-int bng_get_pkt_grid_cap(void);
-void bng_launch_dhcp_service(void*, void*, const void*, void*, void*, void*,
-                             int, int, void*, const void*, uint32_t,
-                             const void*, uint32_t, const void*, void*,
-                             hipStream_t);
-}
+#include "bng_launch.h"
 
 namespace {
 
@@ -292,62 +241,98 @@ void pkt_class(torch::Tensor data, torch::Tensor in_len,
                        cur_stream());
 }
 
+/* Table-management entry points.  The kernels index the batch and rc by
+ * thread id and the table by (hash & mask), so every size is checked here:
+ * a short rc would be an out-of-bounds device write. */
+size_t nbytes(const torch::Tensor& t) {
+  return (size_t)t.numel() * t.element_size();
+}
+
+uint32_t dev_table_mask(const torch::Tensor& t, size_t entry,
+                        const char* name) {
+  check_dev(t, name);
+  return table_mask(t, entry, name);
+}
+
+/* Checks an upsert's batch and rc; returns the record count (0 = nothing
+ * to launch). */
+int upsert_count(const torch::Tensor& batch, size_t entry,
+                 const torch::Tensor& rc) {
+  check_dev(batch, "batch"); check_dev(rc, "rc");
+  TORCH_CHECK(nbytes(batch) % entry == 0, "batch must be a whole number of ",
+              entry, "-byte entries, got ", nbytes(batch), " bytes");
+  size_t n = nbytes(batch) / entry;
+  TORCH_CHECK(n <= (size_t)INT_MAX, "batch too large");
+  TORCH_CHECK(rc.element_size() == 4 && (size_t)rc.numel() >= n,
+              "rc must hold one int32 per record");
+  return (int)n;
+}
+
+/* Checks a delete's keys; returns the key count. */
+int delete_count(const torch::Tensor& keys) {
+  check_dev(keys, "keys");
+  TORCH_CHECK(keys.element_size() == 8, "keys must be 64-bit");
+  TORCH_CHECK(keys.numel() <= INT_MAX, "too many keys");
+  return (int)keys.numel();
+}
+
 void sub_upsert(torch::Tensor table, torch::Tensor batch, torch::Tensor rc) {
-  check_dev(table, "table"); check_dev(batch, "batch");
-  int n = (int)(batch.numel() * batch.element_size() / sizeof(bng_sub_entry));
-  bng_launch_sub_upsert(table.data_ptr(),
-                        table_mask(table, sizeof(bng_sub_entry), "subs"),
-                        batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_sub_entry), "subs");
+  int n = upsert_count(batch, sizeof(bng_sub_entry), rc);
+  if (n == 0) return;
+  bng_launch_sub_upsert(table.data_ptr(), mask, batch.data_ptr(), n,
+                        rc.data_ptr(), cur_stream());
 }
 void sess_import(torch::Tensor sessions, torch::Tensor reverse,
                  torch::Tensor eim, torch::Tensor batch, torch::Tensor rc) {
-  check_dev(sessions, "sessions"); check_dev(reverse, "reverse");
-  check_dev(eim, "eim"); check_dev(batch, "batch");
-  int n = (int)(batch.numel() * batch.element_size() /
-                sizeof(bng_sess_export));
-  bng_launch_sess_import(
-      sessions.data_ptr(),
-      table_mask(sessions, sizeof(bng_nat_session), "sessions"),
-      reverse.data_ptr(),
-      table_mask(reverse, sizeof(bng_nat_reverse), "reverse"),
-      eim.data_ptr(), table_mask(eim, sizeof(bng_eim_entry), "eim"),
-      batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+  uint32_t sess_mask = dev_table_mask(sessions, sizeof(bng_nat_session),
+                                      "sessions");
+  uint32_t rev_mask = dev_table_mask(reverse, sizeof(bng_nat_reverse),
+                                     "reverse");
+  uint32_t eim_mask = dev_table_mask(eim, sizeof(bng_eim_entry), "eim");
+  int n = upsert_count(batch, sizeof(bng_sess_export), rc);
+  if (n == 0) return;
+  bng_launch_sess_import(sessions.data_ptr(), sess_mask, reverse.data_ptr(),
+                         rev_mask, eim.data_ptr(), eim_mask,
+                         batch.data_ptr(), n, rc.data_ptr(), cur_stream());
 }
 void sub_delete(torch::Tensor table, torch::Tensor keys) {
-  bng_launch_sub_delete(table.data_ptr(),
-                        table_mask(table, sizeof(bng_sub_entry), "subs"),
-                        keys.data_ptr(), (int)keys.numel(), cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_sub_entry), "subs");
+  int n = delete_count(keys);
+  if (n == 0) return;
+  bng_launch_sub_delete(table.data_ptr(), mask, keys.data_ptr(), n,
+                        cur_stream());
 }
 void subctx_upsert(torch::Tensor table, torch::Tensor batch,
                    int64_t update_mask, torch::Tensor rc) {
-  int n = (int)(batch.numel() * batch.element_size() /
-                sizeof(bng_subctx));
-  bng_launch_subctx_upsert(
-      table.data_ptr(), table_mask(table, sizeof(bng_subctx), "subctx"),
-      batch.data_ptr(), n, (uint32_t)update_mask, rc.data_ptr(),
-      cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_subctx), "subctx");
+  int n = upsert_count(batch, sizeof(bng_subctx), rc);
+  if (n == 0) return;
+  bng_launch_subctx_upsert(table.data_ptr(), mask, batch.data_ptr(), n,
+                           (uint32_t)update_mask, rc.data_ptr(),
+                           cur_stream());
 }
 void qos_upsert(torch::Tensor table, torch::Tensor batch, torch::Tensor rc) {
-  int n = (int)(batch.numel() * batch.element_size() /
-                sizeof(bng_qos_bucket));
-  bng_launch_qos_upsert(table.data_ptr(),
-                        table_mask(table, sizeof(bng_qos_bucket), "qos"),
-                        batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_qos_bucket), "qos");
+  int n = upsert_count(batch, sizeof(bng_qos_bucket), rc);
+  if (n == 0) return;
+  bng_launch_qos_upsert(table.data_ptr(), mask, batch.data_ptr(), n,
+                        rc.data_ptr(), cur_stream());
 }
 void binding_upsert(torch::Tensor table, torch::Tensor batch,
                     torch::Tensor rc) {
-  int n = (int)(batch.numel() * batch.element_size() /
-                sizeof(bng_binding_entry));
-  bng_launch_binding_upsert(
-      table.data_ptr(),
-      table_mask(table, sizeof(bng_binding_entry), "bindings"),
-      batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_binding_entry), "bindings");
+  int n = upsert_count(batch, sizeof(bng_binding_entry), rc);
+  if (n == 0) return;
+  bng_launch_binding_upsert(table.data_ptr(), mask, batch.data_ptr(), n,
+                            rc.data_ptr(), cur_stream());
 }
 void binding_delete(torch::Tensor table, torch::Tensor keys) {
-  bng_launch_binding_delete(
-      table.data_ptr(),
-      table_mask(table, sizeof(bng_binding_entry), "bindings"),
-      keys.data_ptr(), (int)keys.numel(), cur_stream());
+  uint32_t mask = dev_table_mask(table, sizeof(bng_binding_entry), "bindings");
+  int n = delete_count(keys);
+  if (n == 0) return;
+  bng_launch_binding_delete(table.data_ptr(), mask, keys.data_ptr(), n,
+                            cur_stream());
 }
 
 void nat_sweep(torch::Tensor sessions, torch::Tensor reverse,
@@ -355,15 +340,14 @@ void nat_sweep(torch::Tensor sessions, torch::Tensor reverse,
                int64_t now_ns, int64_t udp_to,
                int64_t tcp_est_to, int64_t tcp_tr_to, int64_t icmp_to,
                torch::Tensor stats) {
-  uint32_t n_slots = (uint32_t)(sessions.numel() * sessions.element_size() /
-                                sizeof(bng_nat_session));
-  uint32_t eim_slots = (uint32_t)(eim.numel() * eim.element_size() /
-                                  sizeof(bng_eim_entry));
+  check_dev(sessions, "sessions"); check_dev(eim, "eim");
+  check_dev(stats, "stats");
+  uint32_t n_slots = (uint32_t)(nbytes(sessions) / sizeof(bng_nat_session));
+  uint32_t eim_slots = (uint32_t)(nbytes(eim) / sizeof(bng_eim_entry));
   bng_launch_nat_sweep(
       sessions.data_ptr(), n_slots, reverse.data_ptr(),
-      table_mask(reverse, sizeof(bng_nat_reverse), "reverse"),
-      subnat.data_ptr(),
-      table_mask(subnat, sizeof(bng_subctx), "subctx"),
+      dev_table_mask(reverse, sizeof(bng_nat_reverse), "reverse"),
+      subnat.data_ptr(), dev_table_mask(subnat, sizeof(bng_subctx), "subctx"),
       eim.data_ptr(), eim_slots, (uint64_t)eim_to,
       (uint64_t)now_ns, (uint64_t)udp_to, (uint64_t)tcp_est_to,
       (uint64_t)tcp_tr_to, (uint64_t)icmp_to, stats.data_ptr(),
@@ -442,20 +426,16 @@ void pppoe_encap(torch::Tensor data, torch::Tensor in_len,
 
 void pppoe_sess_upsert(torch::Tensor sess, torch::Tensor by_ip,
                        torch::Tensor batch, torch::Tensor rc) {
-  check_dev(sess, "pppoe_sess"); check_dev(by_ip, "pppoe_by_ip");
-  check_dev(batch, "batch"); check_dev(rc, "rc");
-  TORCH_CHECK((size_t)sess.numel() * sess.element_size() ==
+  check_dev(sess, "pppoe_sess");
+  TORCH_CHECK(nbytes(sess) ==
               (size_t)BNG_PPPOE_MAX_SESSIONS * sizeof(bng_pppoe_sess),
               "pppoe_sess must hold 65536 entries");
-  int n = (int)(batch.numel() * batch.element_size() /
-                sizeof(bng_pppoe_sess));
-  TORCH_CHECK(rc.numel() >= n && rc.element_size() == 4,
-              "rc must hold one int32 per record");
+  uint32_t mask = dev_table_mask(by_ip, sizeof(bng_pppoe_ip), "pppoe_by_ip");
+  int n = upsert_count(batch, sizeof(bng_pppoe_sess), rc);
   if (n == 0) return;
-  bng_launch_pppoe_sess_upsert(
-      sess.data_ptr(), by_ip.data_ptr(),
-      table_mask(by_ip, sizeof(bng_pppoe_ip), "pppoe_by_ip"),
-      batch.data_ptr(), n, rc.data_ptr(), cur_stream());
+  bng_launch_pppoe_sess_upsert(sess.data_ptr(), by_ip.data_ptr(), mask,
+                               batch.data_ptr(), n, rc.data_ptr(),
+                               cur_stream());
 }
 
 void pppoe_sess_delete(torch::Tensor sess, torch::Tensor by_ip,

@@ -24,6 +24,7 @@
 #include "bng_abi.h"
 #include "bng_params.h"
 #include "bng_device.h"
+#include "bng_launch.h"
 
 /* ==================================================== table primitives */
 
@@ -269,6 +270,84 @@ BNG_DEV E* sig_lookup(E* t, uint32_t mask, uint64_t sig) {
     if (k == sig) return e;
     if (k == BNG_KEY_EMPTY) return nullptr;
   }
+  return nullptr;
+}
+
+/* Probes of the host CRUD kernels (one thread per batch record).
+ *
+ * Key accesses: key loads, the claim CAS and tombstone stores are relaxed,
+ * agent scope.  Value fields are plain stores after the claim; there is no
+ * `ready` flag — stream order publishes the entry to the packet kernels.
+ *
+ * Batch contract: a batch must not name the same key twice.  On a lost CAS
+ * the thread forgets its remembered tombstone and goes on with the NEXT
+ * slot; it does not re-read the lost one, so a duplicate key in one batch
+ * could land in two slots.
+ *
+ * 64-bit-key tables (K = &E::<key field>; 0 empty, ~0 tombstone): an upsert
+ * takes the first tombstone of its chain, but only once an empty slot
+ * proves the key absent.  Known limitation: a chain with tombstones but NO
+ * empty slot within BNG_MAX_PROBE reports full (nullptr) although it is
+ * reclaimable; sig_find_or_claim handles that case, and this is the one
+ * place to fix it. */
+template <auto K, typename E>
+BNG_DEV E* key_upsert_slot(E* t, uint32_t mask, uint64_t key) {
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  E* tomb = nullptr;
+  for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+    E* e = &t[(slot + i) & mask];
+    uint64_t cur = rlx_load64(&(e->*K));
+    if (cur == key) return e;
+    if (cur == BNG_KEY_TOMBSTONE && !tomb) tomb = e;
+    if (cur == BNG_KEY_EMPTY) {
+      E* d = tomb ? tomb : e;
+      uint64_t expect = tomb ? BNG_KEY_TOMBSTONE : BNG_KEY_EMPTY;
+      if (__hip_atomic_compare_exchange_strong(
+              &(d->*K), &expect, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+              __HIP_MEMORY_SCOPE_AGENT))
+        return d;
+      tomb = nullptr;   /* raced with another upsert of this batch */
+    }
+  }
+  return nullptr;       /* probe bound exceeded: table too full */
+}
+
+/* Find for the deletes (the caller stores the tombstone): walks past
+ * tombstones, stops at empty; an absent key is nullptr. */
+template <auto K, typename E>
+BNG_DEV E* key_find(E* t, uint32_t mask, uint64_t key) {
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+    E* e = &t[(slot + i) & mask];
+    uint64_t cur = rlx_load64(&(e->*K));
+    if (cur == key) return e;
+    if (cur == BNG_KEY_EMPTY) return nullptr;
+  }
+  return nullptr;
+}
+
+/* 32-bit key_ip tables (bng_subctx, bng_qos_bucket; 0 empty, no
+ * tombstones).  nullptr with *full unset: the key is absent and
+ * claim_if_absent was false. */
+template <typename E>
+BNG_DEV E* ipkey_upsert_slot(E* t, uint32_t mask, uint32_t ip,
+                             bool claim_if_absent, bool* full) {
+  *full = false;
+  uint32_t slot = (uint32_t)bng_mix64(ip) & mask;
+  for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+    E* e = &t[(slot + i) & mask];
+    uint32_t cur = __hip_atomic_load(&e->key_ip, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == ip) return e;
+    if (cur == 0) {
+      if (!claim_if_absent) return nullptr;
+      if (__hip_atomic_compare_exchange_strong(
+              &e->key_ip, &cur, ip, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+              __HIP_MEMORY_SCOPE_AGENT))
+        return e;
+    }
+  }
+  *full = true;
   return nullptr;
 }
 
@@ -1798,7 +1877,6 @@ __global__ void sess_import_kernel(
       bng_publish_ready(&m->ready);
     }
   }
-  if (rc && rc[i] == 0) rc[i] = 0;
 }
 
 __global__ void sub_upsert_kernel(bng_sub_entry* t, uint32_t mask,
@@ -1807,135 +1885,72 @@ __global__ void sub_upsert_kernel(bng_sub_entry* t, uint32_t mask,
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bng_sub_entry e = batch[i];
-  uint32_t slot = (uint32_t)bng_mix64(e.key) & mask;
-  int first_tomb = -1;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_sub_entry* s = &t[(slot + k) & mask];
-    uint64_t cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == e.key) {   /* overwrite value */
-      s->pool_id = e.pool_id; s->allocated_ip = e.allocated_ip;
-      s->lease_expiry = e.lease_expiry; s->vlan_id = e.vlan_id;
-      s->client_class = e.client_class; s->flags = e.flags;
-      if (rc) rc[i] = 0;
-      return;
-    }
-    if (cur == BNG_KEY_TOMBSTONE && first_tomb < 0)
-      first_tomb = (int)((slot + k) & mask);
-    if (cur == BNG_KEY_EMPTY) {
-      int target = first_tomb >= 0 ? first_tomb : (int)((slot + k) & mask);
-      bng_sub_entry* d = &t[target];
-      uint64_t expect = first_tomb >= 0 ? BNG_KEY_TOMBSTONE : BNG_KEY_EMPTY;
-      if (__hip_atomic_compare_exchange_strong(
-              &d->key, &expect, e.key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT)) {
-        d->pool_id = e.pool_id; d->allocated_ip = e.allocated_ip;
-        d->lease_expiry = e.lease_expiry; d->vlan_id = e.vlan_id;
-        d->client_class = e.client_class; d->flags = e.flags;
-        if (rc) rc[i] = 0;
-        return;
-      }
-      /* raced with another upsert in this batch; retry from here */
-      first_tomb = -1;
-      continue;
-    }
+  bng_sub_entry* s = key_upsert_slot<&bng_sub_entry::key>(t, mask, e.key);
+  if (s) {
+    s->pool_id = e.pool_id; s->allocated_ip = e.allocated_ip;
+    s->lease_expiry = e.lease_expiry; s->vlan_id = e.vlan_id;
+    s->client_class = e.client_class; s->flags = e.flags;
   }
-  if (rc) rc[i] = -1;   /* probe bound exceeded: table too full */
+  if (rc) rc[i] = s ? 0 : -1;
 }
 
 __global__ void sub_delete_kernel(bng_sub_entry* t, uint32_t mask,
                                   const uint64_t* keys, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint64_t key = keys[i];
-  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_sub_entry* s = &t[(slot + k) & mask];
-    uint64_t cur = s->key;
-    if (cur == key) {
-      __hip_atomic_store(&s->key, BNG_KEY_TOMBSTONE, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    if (cur == BNG_KEY_EMPTY) return;
-  }
+  bng_sub_entry* s = key_find<&bng_sub_entry::key>(t, mask, keys[i]);
+  if (s) rlx_store64(&s->key, BNG_KEY_TOMBSTONE);
 }
 
 /* Merge-upsert into the subscriber context.  update_mask selects which
  * half changes (BNG_CTX_SET_NAT / SET_QOS / CLR_QOS / CLR_NAT) so the
  * NAT manager and the QoS manager can each own their fields without
- * clobbering the other's — the BPF-map analog of two maps sharing a key. */
+ * clobbering the other's — the BPF-map analog of two maps sharing a key.
+ * A clear-only mask on an absent key claims nothing and returns 0. */
 __global__ void subctx_upsert_kernel(bng_subctx* t, uint32_t mask,
                                      const bng_subctx* batch, int n,
                                      uint32_t um, int* rc) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bng_subctx e = batch[i];
-  uint32_t slot = (uint32_t)bng_mix64(e.key_ip) & mask;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_subctx* s = &t[(slot + k) & mask];
-    uint32_t cur = __hip_atomic_load(&s->key_ip, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == e.key_ip || cur == 0) {
-      if (cur == 0) {
-        if (!(um & (BNG_CTX_SET_NAT | BNG_CTX_SET_QOS))) {
-          if (rc) rc[i] = 0;   /* clear of an absent entry: no-op */
-          return;
-        }
-        uint32_t expect = 0;
-        if (!__hip_atomic_compare_exchange_strong(
-                &s->key_ip, &expect, e.key_ip, __ATOMIC_RELAXED,
-                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-          continue;
-      }
-      if (um & BNG_CTX_SET_NAT) {
-        s->public_ip = e.public_ip;
-        s->port_start = e.port_start; s->port_end = e.port_end;
-        s->next_port = e.next_port; s->subscriber_id = e.subscriber_id;
-        s->flags = e.flags; s->nat_valid = 1;
-      }
-      if (um & BNG_CTX_SET_QOS) {
-        s->rate_bps = e.rate_bps; s->tokens = e.tokens;
-        s->last_update = e.last_update; s->burst_bytes = e.burst_bytes;
-        s->priority = e.priority; s->qos_valid = 1;
-      }
-      if (um & BNG_CTX_CLR_QOS) s->qos_valid = 0;
-      if (um & BNG_CTX_CLR_NAT) s->nat_valid = 0;
-      if (rc) rc[i] = 0;
-      return;
+  bool full;
+  bng_subctx* s = ipkey_upsert_slot(
+      t, mask, e.key_ip, (um & (BNG_CTX_SET_NAT | BNG_CTX_SET_QOS)) != 0,
+      &full);
+  if (s) {
+    if (um & BNG_CTX_SET_NAT) {
+      s->public_ip = e.public_ip;
+      s->port_start = e.port_start; s->port_end = e.port_end;
+      s->next_port = e.next_port; s->subscriber_id = e.subscriber_id;
+      s->flags = e.flags; s->nat_valid = 1;
     }
+    if (um & BNG_CTX_SET_QOS) {
+      s->rate_bps = e.rate_bps; s->tokens = e.tokens;
+      s->last_update = e.last_update; s->burst_bytes = e.burst_bytes;
+      s->priority = e.priority; s->qos_valid = 1;
+    }
+    if (um & BNG_CTX_CLR_QOS) s->qos_valid = 0;
+    if (um & BNG_CTX_CLR_NAT) s->nat_valid = 0;
   }
-  if (rc) rc[i] = -1;
+  if (rc) rc[i] = full ? -1 : 0;
 }
 
+/* Any upsert claims a slot; valid=0 is how a policy is removed. */
 __global__ void qos_upsert_kernel(bng_qos_bucket* t, uint32_t mask,
                                   const bng_qos_bucket* batch, int n,
                                   int* rc) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bng_qos_bucket e = batch[i];
-  uint32_t slot = (uint32_t)bng_mix64(e.key_ip) & mask;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_qos_bucket* s = &t[(slot + k) & mask];
-    uint32_t cur = __hip_atomic_load(&s->key_ip, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == e.key_ip || cur == 0) {
-      if (cur == 0) {
-        uint32_t expect = 0;
-        if (!__hip_atomic_compare_exchange_strong(
-                &s->key_ip, &expect, e.key_ip, __ATOMIC_RELAXED,
-                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-          continue;
-      }
-      s->rate_bps = e.rate_bps; s->tokens = e.tokens;
-      s->last_update = e.last_update; s->burst_bytes = e.burst_bytes;
-      s->priority = e.priority;
-      s->valid = e.valid;     /* valid=0 upsert == remove policy */
-      if (rc) rc[i] = 0;
-      return;
-    }
+  bool full;
+  bng_qos_bucket* s = ipkey_upsert_slot(t, mask, e.key_ip, true, &full);
+  if (s) {
+    s->rate_bps = e.rate_bps; s->tokens = e.tokens;
+    s->last_update = e.last_update; s->burst_bytes = e.burst_bytes;
+    s->priority = e.priority;
+    s->valid = e.valid;
   }
-  if (rc) rc[i] = -1;
+  if (rc) rc[i] = full ? -1 : 0;
 }
 
 __global__ void binding_upsert_kernel(bng_binding_entry* t, uint32_t mask,
@@ -1944,59 +1959,24 @@ __global__ void binding_upsert_kernel(bng_binding_entry* t, uint32_t mask,
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bng_binding_entry e = batch[i];
-  uint32_t slot = (uint32_t)bng_mix64(e.key_mac) & mask;
-  int first_tomb = -1;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_binding_entry* s = &t[(slot + k) & mask];
-    uint64_t cur = __hip_atomic_load(&s->key_mac, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == e.key_mac) {
-      s->ipv4_addr = e.ipv4_addr; s->ipv4_valid = e.ipv4_valid;
-      s->ipv6_valid = e.ipv6_valid; s->mode = e.mode;
-      #pragma unroll
-      for (int j = 0; j < 16; ++j) s->ipv6_addr[j] = e.ipv6_addr[j];
-      if (rc) rc[i] = 0;
-      return;
-    }
-    if (cur == BNG_KEY_TOMBSTONE && first_tomb < 0)
-      first_tomb = (int)((slot + k) & mask);
-    if (cur == BNG_KEY_EMPTY) {
-      int target = first_tomb >= 0 ? first_tomb : (int)((slot + k) & mask);
-      bng_binding_entry* d = &t[target];
-      uint64_t expect = first_tomb >= 0 ? BNG_KEY_TOMBSTONE : BNG_KEY_EMPTY;
-      if (__hip_atomic_compare_exchange_strong(
-              &d->key_mac, &expect, e.key_mac, __ATOMIC_RELAXED,
-              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        d->ipv4_addr = e.ipv4_addr; d->ipv4_valid = e.ipv4_valid;
-        d->ipv6_valid = e.ipv6_valid; d->mode = e.mode;
-        #pragma unroll
-        for (int j = 0; j < 16; ++j) d->ipv6_addr[j] = e.ipv6_addr[j];
-        if (rc) rc[i] = 0;
-        return;
-      }
-      first_tomb = -1;
-      continue;
-    }
+  bng_binding_entry* s =
+      key_upsert_slot<&bng_binding_entry::key_mac>(t, mask, e.key_mac);
+  if (s) {
+    s->ipv4_addr = e.ipv4_addr; s->ipv4_valid = e.ipv4_valid;
+    s->ipv6_valid = e.ipv6_valid; s->mode = e.mode;
+    #pragma unroll
+    for (int j = 0; j < 16; ++j) s->ipv6_addr[j] = e.ipv6_addr[j];
   }
-  if (rc) rc[i] = -1;
+  if (rc) rc[i] = s ? 0 : -1;
 }
 
 __global__ void binding_delete_kernel(bng_binding_entry* t, uint32_t mask,
                                       const uint64_t* keys, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint64_t key = keys[i];
-  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_binding_entry* s = &t[(slot + k) & mask];
-    uint64_t cur = s->key_mac;
-    if (cur == key) {
-      __hip_atomic_store(&s->key_mac, BNG_KEY_TOMBSTONE, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    if (cur == BNG_KEY_EMPTY) return;
-  }
+  bng_binding_entry* s =
+      key_find<&bng_binding_entry::key_mac>(t, mask, keys[i]);
+  if (s) rlx_store64(&s->key_mac, BNG_KEY_TOMBSTONE);
 }
 
 /* NAT session sweeper: reclaim timed-out sessions (the LRU-map analog,
@@ -2305,26 +2285,17 @@ void pppoe_encap_kernel(uint8_t* data, uint16_t* in_len, uint8_t* verdict,
   sb_commit(sb, 0, BNG_PPPOE_NSTATS, stats);
 }
 
-/* Stream-ordered session CRUD, one thread per batch record.  A batch must
- * not name the same session id or the same IP twice. */
+/* Stream-ordered session CRUD, one thread per batch record, under the
+ * batch contract of the host CRUD probes: a batch must not name the same
+ * session id or the same IP twice. */
 BNG_DEV void pppoe_ip_remove(bng_pppoe_ip* t, uint32_t mask, uint32_t ip,
                              uint32_t sid) {
-  uint64_t key = BNG_PPPOE_IP_KEY(ip);
-  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
-  for (int k = 0; k < BNG_MAX_PROBE; ++k) {
-    bng_pppoe_ip* s = &t[(slot + k) & mask];
-    uint64_t cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == key) {
-      /* only the owner removes it: the address may already belong to a
-       * newer session */
-      if ((uint32_t)(s->sid_mac >> 48) == sid)
-        __hip_atomic_store(&s->key, BNG_KEY_TOMBSTONE, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    if (cur == BNG_KEY_EMPTY) return;
-  }
+  bng_pppoe_ip* s =
+      key_find<&bng_pppoe_ip::key>(t, mask, BNG_PPPOE_IP_KEY(ip));
+  /* only the owner removes it: the address may already belong to a newer
+   * session */
+  if (s && (uint32_t)(s->sid_mac >> 48) == sid)
+    rlx_store64(&s->key, BNG_KEY_TOMBSTONE);
 }
 
 __global__ void pppoe_sess_upsert_kernel(bng_pppoe_sess* sess,
@@ -2340,39 +2311,16 @@ __global__ void pppoe_sess_upsert_kernel(bng_pppoe_sess* sess,
   /* same id, other address: the stale by-IP entry must go */
   if ((old.mac_valid & BNG_PPPOE_VALID) && old.ip != e.ip)
     pppoe_ip_remove(t, mask, old.ip, sid);
-  uint64_t key = BNG_PPPOE_IP_KEY(e.ip);
-  uint64_t val = ((uint64_t)sid << 48) | mac;
-  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
-  int first_tomb = -1;
-  bool done = false;
-  for (int k = 0; k < BNG_MAX_PROBE && !done; ++k) {
-    bng_pppoe_ip* s = &t[(slot + k) & mask];
-    uint64_t cur = __hip_atomic_load(&s->key, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == key) { s->sid_mac = val; done = true; break; }
-    if (cur == BNG_KEY_TOMBSTONE && first_tomb < 0)
-      first_tomb = (int)((slot + k) & mask);
-    if (cur == BNG_KEY_EMPTY) {
-      int target = first_tomb >= 0 ? first_tomb : (int)((slot + k) & mask);
-      bng_pppoe_ip* d = &t[target];
-      uint64_t expect = first_tomb >= 0 ? BNG_KEY_TOMBSTONE : BNG_KEY_EMPTY;
-      if (__hip_atomic_compare_exchange_strong(
-              &d->key, &expect, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT)) {
-        d->sid_mac = val; done = true; break;
-      }
-      /* raced with another upsert in this batch; retry from here */
-      first_tomb = -1;
-      continue;
-    }
-  }
-  if (!done) {
+  bng_pppoe_ip* s =
+      key_upsert_slot<&bng_pppoe_ip::key>(t, mask, BNG_PPPOE_IP_KEY(e.ip));
+  if (!s) {
     /* by-IP chain full: leave the session out of both tables so the two
      * directions stay consistent */
     sess[sid] = bng_pppoe_sess{0, 0, 0, 0};
     if (rc) rc[i] = -1;
     return;
   }
+  s->sid_mac = ((uint64_t)sid << 48) | mac;
   e.mac_valid = mac | BNG_PPPOE_VALID;
   sess[sid] = e;
   if (rc) rc[i] = 0;

@@ -122,6 +122,17 @@ class HipLauncher:
         t = self.torch.from_numpy(np.frombuffer(bytearray(raw), dtype=np.uint8))
         return t.to(self.device, non_blocking=True)
 
+    def _upsert_one(self, upsert, table, entry: ctypes.Structure, *extra):
+        """Upload one entry and enqueue an ext.*_upsert for it.  rc is not
+        read back: that would be a device sync per control-plane call."""
+        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
+        upsert(table, self._to_dev(_struct_bytes(entry)), *extra, rc)
+
+    def _key_tensor(self, key: int):
+        import numpy as np
+        return self.torch.from_numpy(
+            np.array([key], dtype=np.uint64).view(np.int64)).to(self.device)
+
     # =================================================== DHCP (loader.go)
     def add_subscriber(self, mac, pool_id: int, ip: int, lease_expiry: int,
                        vlan_id: int = 0, client_class: int = 0,
@@ -157,9 +168,7 @@ class HipLauncher:
         e = abi.SubEntry(key=key, pool_id=pool_id, allocated_ip=ip,
                          lease_expiry=lease_expiry, vlan_id=vlan_id,
                          client_class=client_class, flags=flags)
-        batch = self._to_dev(_struct_bytes(e))
-        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
-        self.ext.sub_upsert(self.subs, batch, rc)
+        self._upsert_one(self.ext.sub_upsert, self.subs, e)
 
     def remove_subscriber(self, mac):
         key = mac if isinstance(mac, int) else abi.mac_to_u64(bytes(mac))
@@ -175,10 +184,7 @@ class HipLauncher:
         self._del_sub_key(key)
 
     def _del_sub_key(self, key: int):
-        import numpy as np
-        keys = self.torch.from_numpy(
-            np.array([key], dtype=np.uint64).view(np.int64)).to(self.device)
-        self.ext.sub_delete(self.subs, keys)
+        self.ext.sub_delete(self.subs, self._key_tensor(key))
 
     def add_pool(self, pool_id: int, network: int, prefix_len: int,
                  gateway: int, dns_primary: int = 0, dns_secondary: int = 0,
@@ -235,9 +241,8 @@ class HipLauncher:
         e = abi.SubCtx(key_ip=private_ip, subscriber_id=subscriber_id,
                        public_ip=public_ip, port_start=port_start,
                        port_end=port_end, next_port=port_start)
-        batch = self._to_dev(_struct_bytes(e))
-        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
-        self.ext.subctx_upsert(self.subctx, batch, abi.CTX_SET_NAT, rc)
+        self._upsert_one(self.ext.subctx_upsert, self.subctx, e,
+                         abi.CTX_SET_NAT)
 
     def set_hairpin_ips(self, ips: Sequence[int]):
         import numpy as np
@@ -292,30 +297,25 @@ class HipLauncher:
                        now_ns: Optional[int] = None):
         """ref qos/manager.go:248 SetSubscriberPolicy."""
         now = now_ns if now_ns is not None else time.time_ns()
-        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
         if direction == "egress":
             b = abi.QosBucket(key_ip=ip, valid=1, priority=priority,
                               rate_bps=rate_bps, tokens=burst_bytes,
                               last_update=now, burst_bytes=burst_bytes)
-            self.ext.qos_upsert(self.qos_egress, self._to_dev(
-                _struct_bytes(b)), rc)
+            self._upsert_one(self.ext.qos_upsert, self.qos_egress, b)
         else:
             e = abi.SubCtx(key_ip=ip, priority=priority, rate_bps=rate_bps,
                            tokens=burst_bytes, last_update=now,
                            burst_bytes=burst_bytes)
-            self.ext.subctx_upsert(self.subctx, self._to_dev(
-                _struct_bytes(e)), abi.CTX_SET_QOS, rc)
+            self._upsert_one(self.ext.subctx_upsert, self.subctx, e,
+                             abi.CTX_SET_QOS)
 
     def remove_qos_policy(self, ip: int, direction: str = "egress"):
-        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
         if direction == "egress":
-            b = abi.QosBucket(key_ip=ip, valid=0)
-            self.ext.qos_upsert(self.qos_egress, self._to_dev(
-                _struct_bytes(b)), rc)
+            self._upsert_one(self.ext.qos_upsert, self.qos_egress,
+                             abi.QosBucket(key_ip=ip, valid=0))
         else:
-            e = abi.SubCtx(key_ip=ip)
-            self.ext.subctx_upsert(self.subctx, self._to_dev(
-                _struct_bytes(e)), abi.CTX_CLR_QOS, rc)
+            self._upsert_one(self.ext.subctx_upsert, self.subctx,
+                             abi.SubCtx(key_ip=ip), abi.CTX_CLR_QOS)
 
     def qos_get_stats(self) -> Dict[str, int]:
         return dict(zip(abi.QOS_STAT_NAMES, self.qos_stats.cpu().tolist()))
@@ -342,16 +342,11 @@ class HipLauncher:
                              ipv6_valid=1 if ipv6 else 0, mode=mode)
         for i, by in enumerate((ipv6 or b"")[:16]):
             b.ipv6_addr[i] = by
-        batch = self._to_dev(_struct_bytes(b))
-        rc = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
-        self.ext.binding_upsert(self.bindings, batch, rc)
+        self._upsert_one(self.ext.binding_upsert, self.bindings, b)
 
     def remove_binding(self, mac):
-        import numpy as np
         key = mac if isinstance(mac, int) else abi.mac_to_u64(bytes(mac))
-        keys = self.torch.from_numpy(
-            np.array([key], dtype=np.uint64).view(np.int64)).to(self.device)
-        self.ext.binding_delete(self.bindings, keys)
+        self.ext.binding_delete(self.bindings, self._key_tensor(key))
 
     def antispoof_get_stats(self) -> Dict[str, int]:
         return dict(zip(abi.AS_STAT_NAMES, self.as_stats.cpu().tolist()))
@@ -571,18 +566,15 @@ class HipLauncher:
         """Download the subscriber fast-path table for HA sync (the GPU
         analog of the reference's session-store snapshot feeding
         HASyncer full syncs)."""
-        import numpy as np
-        raw = self.subs.cpu().numpy()
-        arr = raw.view([("key", "<u8"), ("pool_id", "<u4"),
-                        ("ip", "<u4"), ("lease", "<u8"),
-                        ("vlan", "<u2"), ("cc", "u1"), ("fl", "u1"),
-                        ("pad", "<u4")])
+        arr = self.subs.cpu().numpy().view(abi.SUB_ENTRY_DTYPE)
         live = arr[(arr["key"] != 0) &
                    (arr["key"] != 0xFFFFFFFFFFFFFFFF)]
         return [{"key": int(e["key"]), "pool_id": int(e["pool_id"]),
-                 "ip": int(e["ip"]), "lease_expiry": int(e["lease"]),
-                 "vlan_id": int(e["vlan"]),
-                 "client_class": int(e["cc"]), "flags": int(e["fl"])}
+                 "ip": int(e["allocated_ip"]),
+                 "lease_expiry": int(e["lease_expiry"]),
+                 "vlan_id": int(e["vlan_id"]),
+                 "client_class": int(e["client_class"]),
+                 "flags": int(e["flags"])}
                 for e in live]
 
     def import_subscribers(self, entries: Sequence[dict]) -> int:
@@ -592,10 +584,7 @@ class HipLauncher:
         if not entries:
             return 0
         n = len(entries)
-        arr = np.zeros(n, dtype=[("key", "<u8"), ("pool_id", "<u4"),
-                                 ("ip", "<u4"), ("lease", "<u8"),
-                                 ("vlan", "<u2"), ("cc", "u1"),
-                                 ("fl", "u1"), ("pad", "<u4")])
+        arr = np.zeros(n, dtype=abi.SUB_ENTRY_DTYPE)
         for i, e in enumerate(entries):
             arr[i] = (e["key"], e.get("pool_id", 0), e.get("ip", 0),
                       e.get("lease_expiry", 0), e.get("vlan_id", 0),

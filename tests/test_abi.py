@@ -104,3 +104,40 @@ class TestConversions:
                 for i in range(1000)}
         assert len(keys) == 1000
         assert fnv1a64(b"") == 0xcbf29ce484222325   # FNV offset basis
+
+
+def test_sub_entry_dtype_matches_ctypes():
+    """abi.SUB_ENTRY_DTYPE is bng_sub_entry as a numpy record: 32 bytes,
+    every field where abi.SubEntry has it."""
+    import numpy as np
+    dt = np.dtype(abi.SUB_ENTRY_DTYPE)
+    assert dt.itemsize == 32 == ctypes.sizeof(abi.SubEntry)
+    assert list(dt.names) == [f[0] for f in abi.SubEntry._fields_]
+    for name, ctype in abi.SubEntry._fields_:
+        assert dt.fields[name][1] == getattr(abi.SubEntry, name).offset, name
+        assert dt.fields[name][0].itemsize == ctypes.sizeof(ctype), name
+
+
+def test_sources_mtime_sees_every_header(tmp_path, monkeypatch):
+    """An edit to any csrc header (bng_params.h was once missed) makes the
+    built _C.so stale.  No compile: a copy of csrc and a fake _C.so."""
+    import os
+    import shutil
+    from bng_amd.dataplane import build
+    csrc = tmp_path / "csrc"
+    shutil.copytree(build.CSRC, csrc)
+    so = tmp_path / "_C.so"
+    so.write_bytes(b"")
+    for f in csrc.iterdir():
+        os.utime(f, (1_000_000, 1_000_000))
+    os.utime(so, (2_000_000, 2_000_000))
+    monkeypatch.setattr(build, "CSRC", str(csrc))
+    monkeypatch.setattr(build, "SOURCES",
+                        [str(csrc / os.path.basename(s))
+                         for s in build.SOURCES])
+    assert build._sources_mtime() < os.path.getmtime(so)
+    for hdr in sorted(p.name for p in csrc.glob("*.h")):
+        os.utime(csrc / hdr, (3_000_000, 3_000_000))
+        assert build._sources_mtime() > os.path.getmtime(so), hdr
+        os.utime(csrc / hdr, (1_000_000, 1_000_000))
+    assert "bng_params.h" in {p.name for p in csrc.glob("*.h")}
