@@ -23,12 +23,6 @@ BNG_DEV uint64_t bng_mix64(uint64_t x) {
   return z ^ (z >> 31);
 }
 
-BNG_DEV uint64_t bng_fnv1a64(const uint8_t* p, int n) {
-  uint64_t h = 0xCBF29CE484222325ULL;
-  for (int i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001B3ULL; }
-  return h;
-}
-
 BNG_DEV uint64_t bng_tuple_sig(uint32_t src_ip, uint32_t dst_ip,
                                uint16_t src_port, uint16_t dst_port,
                                uint8_t proto) {

@@ -382,21 +382,42 @@ struct pktctx {
   bool regs;
 };
 
-/* constant-offset register accessors (offsets fold at compile time) */
+/* constant-offset register accessors (offsets fold at compile time).
+ * The w_* forms work on any window of bswapped words, `o` counted from
+ * the window's first byte; the rg_* forms are the packet's bytes 0..47. */
+template <int N> BNG_DEV uint32_t w_ld8(const uint32_t (&W)[N], int o) {
+  return (W[o >> 2] >> (24 - 8 * (o & 3))) & 0xFFu;
+}
+template <int N> BNG_DEV uint32_t w_ld16(const uint32_t (&W)[N], int o) {
+  return (w_ld8(W, o) << 8) | w_ld8(W, o + 1);
+}
+template <int N> BNG_DEV uint32_t w_ld32(const uint32_t (&W)[N], int o) {
+  return (w_ld16(W, o) << 16) | w_ld16(W, o + 2);
+}
+template <int N> BNG_DEV void w_st8(uint32_t (&W)[N], int o, uint32_t v) {
+  int i = o >> 2, sh = 24 - 8 * (o & 3);
+  W[i] = (W[i] & ~(0xFFu << sh)) | ((v & 0xFFu) << sh);
+}
+template <int N> BNG_DEV void w_st16(uint32_t (&W)[N], int o, uint32_t v) {
+  w_st8(W, o, v >> 8); w_st8(W, o + 1, v);
+}
+template <int N> BNG_DEV void w_st32(uint32_t (&W)[N], int o, uint32_t v) {
+  w_st16(W, o, v >> 16); w_st16(W, o + 2, v);
+}
+/* words 4k..4k+3 of a window as the 16 B they came from */
+template <int N> BNG_DEV uint4 w_chunk(const uint32_t (&W)[N], int k) {
+  return make_uint4(__builtin_bswap32(W[4 * k]),
+                    __builtin_bswap32(W[4 * k + 1]),
+                    __builtin_bswap32(W[4 * k + 2]),
+                    __builtin_bswap32(W[4 * k + 3]));
+}
 #define RG_B(c, o) (((c).W[(o) >> 2] >> (24 - 8 * ((o) & 3))) & 0xFFu)
 BNG_DEV uint16_t rg_ld16(const pktctx& c, int o) {
   return (uint16_t)((RG_B(c, o) << 8) | RG_B(c, o + 1));
 }
-BNG_DEV void rg_st8(pktctx& c, int o, uint32_t v) {
-  int i = o >> 2, sh = 24 - 8 * (o & 3);
-  c.W[i] = (c.W[i] & ~(0xFFu << sh)) | ((v & 0xFFu) << sh);
-}
-BNG_DEV void rg_st16(pktctx& c, int o, uint32_t v) {
-  rg_st8(c, o, v >> 8); rg_st8(c, o + 1, v);
-}
-BNG_DEV void rg_st32(pktctx& c, int o, uint32_t v) {
-  rg_st16(c, o, v >> 16); rg_st16(c, o + 2, v);
-}
+BNG_DEV void rg_st8(pktctx& c, int o, uint32_t v) { w_st8(c.W, o, v); }
+BNG_DEV void rg_st16(pktctx& c, int o, uint32_t v) { w_st16(c.W, o, v); }
+BNG_DEV void rg_st32(pktctx& c, int o, uint32_t v) { w_st32(c.W, o, v); }
 BNG_DEV void rg_flush16_47(pktctx& c) {
   uint4* q = (uint4*)c.p;
   q[1] = make_uint4(__builtin_bswap32(c.W[4]), __builtin_bswap32(c.W[5]),
@@ -553,13 +574,149 @@ BNG_DEV void scan_dhcp_options(const uint8_t* p, int opt_off, int end,
   }
 }
 
-/* Per-packet DHCP fast path.  Returns verdict; *out_len set on TX. */
-BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
-                         const dhcp_tables& T, dhcp_flags& F,
-                         uint16_t* out_len) {
+/* ---- wide reply builder.  When the fast parse ran (untagged, ihl 5,
+ * 16-B aligned row) every offset of the reply is a constant: Ethernet 0,
+ * IP 14, UDP 34, BOOTP 42 (op 42, hops 45, flags 52, ciaddr 54, yiaddr 58,
+ * siaddr 62, giaddr 66, chaddr 70, sname 86, file 150, cookie 278,
+ * options 282).  The reply is then composed in registers and leaves as
+ * 16-B stores instead of ~110 byte/short/dword stores per packet:
+ *   bytes   0..47   the parse's register window (headers, op, hops)
+ *   bytes  48..95   loaded before the lookup (it also feeds chaddr,
+ *                   giaddr, flags and ciaddr), patched, stored back
+ *   bytes  96..271  zeros (sname/file)
+ *   bytes 272..     tail of `file`, the cookie, the options
+ * It writes exactly the bytes the byte-wise builder writes, no byte
+ * more: the last, partial 16 B go out as exact-width stores.  The row
+ * must hold the longest reply. */
+enum {
+  BNG_DHCP_OPT_OFF = 282,          /* untagged ihl-5 frame */
+  BNG_DHCP_MAX_OPTS = 50,          /* with two DNS servers */
+  BNG_DHCP_WIDE_MIN_STRIDE = 336   /* 272 + 4 chunks */
+};
+
+struct dhcp_reply {                /* what both builders put on the wire */
+  uint32_t yiaddr, server_ip;
+  uint8_t reply_type;
+};
+
+BNG_DEV uint32_t pool_netmask(const bng_ip_pool& pool) {
+  return (pool.prefix_len == 0) ? 0
+      : (pool.prefix_len >= 32) ? 0xFFFFFFFFu
+      : (0xFFFFFFFFu << (32 - pool.prefix_len));
+}
+
+/* options 53/54/51/1/3/[6]/58/59/255 into the window O (bytes 272..335 of
+ * the row), NDNS servers in option 6; then the stores from byte 272 on */
+template <int NDNS>
+BNG_DEV void dhcp_wide_options(uint8_t* p, const dhcp_reply& R,
+                               const bng_ip_pool& pool) {
+  uint32_t O[16];
+  #pragma unroll
+  for (int i = 0; i < 16; ++i) O[i] = 0;
+  int o = 6;                       /* 272..277: end of `file`, zero */
+  w_st32(O, o, 0x63825363u); o += 4;
+  w_st8(O, o, 53); w_st8(O, o + 1, 1); w_st8(O, o + 2, R.reply_type); o += 3;
+  w_st8(O, o, 54); w_st8(O, o + 1, 4); w_st32(O, o + 2, R.server_ip); o += 6;
+  w_st8(O, o, 51); w_st8(O, o + 1, 4); w_st32(O, o + 2, pool.lease_time);
+  o += 6;
+  w_st8(O, o, 1); w_st8(O, o + 1, 4); w_st32(O, o + 2, pool_netmask(pool));
+  o += 6;
+  w_st8(O, o, 3); w_st8(O, o + 1, 4); w_st32(O, o + 2, pool.gateway); o += 6;
+  if (NDNS) {
+    w_st8(O, o, 6); w_st8(O, o + 1, 4 * NDNS);
+    w_st32(O, o + 2, pool.dns_primary);
+    if (NDNS == 2) w_st32(O, o + 6, pool.dns_secondary);
+    o += 2 + 4 * NDNS;
+  }
+  w_st8(O, o, 58); w_st8(O, o + 1, 4); w_st32(O, o + 2, pool.lease_time / 2);
+  o += 6;
+  w_st8(O, o, 59); w_st8(O, o + 1, 4);
+  w_st32(O, o + 2, (pool.lease_time * 7) / 8); o += 6;
+  w_st8(O, o, 255); o += 1;
+  /* o = 50 / 56 / 60: three whole chunks, then 2 / 8 / 12 bytes */
+  uint4* q = (uint4*)(p + 272);
+  q[0] = w_chunk(O, 0); q[1] = w_chunk(O, 1); q[2] = w_chunk(O, 2);
+  uint4 t = w_chunk(O, 3);
+  if (NDNS == 0) {
+    *(uint16_t*)(p + 320) = (uint16_t)t.x;
+  } else {
+    *(uint2*)(p + 320) = make_uint2(t.x, t.y);
+    if (NDNS == 2) *(uint32_t*)(p + 328) = t.z;
+  }
+}
+
+/* c.W holds bytes 0..47 and X bytes 48..95 of the request; returns the
+ * frame length of the reply */
+BNG_DEV int dhcp_reply_wide(pktctx& c, uint32_t (&X)[12],
+                            const dhcp_reply& R, const bng_ip_pool& pool,
+                            const bng_server_config& cfg, dhcp_flags& F) {
+  uint8_t* p = c.p;
+  const int ndns = pool.dns_primary ? (pool.dns_secondary ? 2 : 1) : 0;
+  const int w = 40 + (ndns ? 2 + 4 * ndns : 0);
+  uint32_t giaddr = w_ld32(X, 66 - 48);
+  uint32_t smac_hi = ((uint32_t)cfg.server_mac[0] << 8) | cfg.server_mac[1];
+  uint32_t smac_lo = ((uint32_t)cfg.server_mac[2] << 24) |
+                     ((uint32_t)cfg.server_mac[3] << 16) |
+                     ((uint32_t)cfg.server_mac[4] << 8) | cfg.server_mac[5];
+  uint32_t dst_ip, dport;
+  if (giaddr != 0) {   /* relayed: unicast to relay agent (ref :726-743) */
+    uint32_t hi = rg_ld16(c, 6);
+    uint32_t lo = ((uint32_t)rg_ld16(c, 8) << 16) | rg_ld16(c, 10);
+    rg_st16(c, 0, hi); rg_st32(c, 2, lo);
+    dst_ip = giaddr; dport = 67;
+    F.ucast = true;
+  } else {
+    uint32_t flags = w_ld16(X, 52 - 48), ciaddr = w_ld32(X, 54 - 48);
+    if ((flags & 0x8000) || ciaddr == 0) {
+      rg_st16(c, 0, 0xFFFFu); rg_st32(c, 2, 0xFFFFFFFFu);
+      F.bcast = true;
+    } else {
+      rg_st16(c, 0, w_ld16(X, 70 - 48)); rg_st32(c, 2, w_ld32(X, 72 - 48));
+      F.ucast = true;
+    }
+    dst_ip = 0xFFFFFFFFu; dport = 68;
+  }
+  rg_st16(c, 6, smac_hi); rg_st32(c, 8, smac_lo);
+  rg_st32(c, 26, R.server_ip); rg_st32(c, 30, dst_ip);
+  rg_st16(c, 34, 67); rg_st16(c, 36, dport);
+  rg_st8(c, 22, 64);                  /* TTL */
+  rg_st16(c, 40, 0);                  /* UDP csum 0 (ref :741,755) */
+  rg_st8(c, 42, 2);                   /* BOOTREPLY */
+  rg_st8(c, 45, 0);                   /* hops */
+  rg_st16(c, 16, 20 + 8 + 240 + w);   /* IP total length */
+  rg_st16(c, 38, 8 + 240 + w);        /* UDP length */
+  rg_st16(c, 24, 0);
+  /* 10x u16 sum over bytes 14..33, from the window */
+  uint32_t s = 0;
+  #pragma unroll
+  for (int i = 0; i < 10; ++i) s += rg_ld16(c, 14 + 2 * i);
+  s = (s & 0xFFFF) + (s >> 16); s = (s & 0xFFFF) + (s >> 16);
+  rg_st16(c, 24, ~s & 0xFFFFu);
+
+  w_st32(X, 58 - 48, R.yiaddr);
+  w_st32(X, 62 - 48, R.server_ip);
+  w_st16(X, 86 - 48, 0); X[10] = 0; X[11] = 0;   /* sname 86..95 */
+
+  uint4* q = (uint4*)p;
+  q[0] = w_chunk(c.W, 0); q[1] = w_chunk(c.W, 1); q[2] = w_chunk(c.W, 2);
+  q[3] = w_chunk(X, 0); q[4] = w_chunk(X, 1); q[5] = w_chunk(X, 2);
+  #pragma unroll
+  for (int i = 6; i < 17; ++i) q[i] = make_uint4(0, 0, 0, 0);   /* ..271 */
+  if (ndns == 0) dhcp_wide_options<0>(p, R, pool);
+  else if (ndns == 1) dhcp_wide_options<1>(p, R, pool);
+  else dhcp_wide_options<2>(p, R, pool);
+  return BNG_DHCP_OPT_OFF + w;
+}
+
+/* Per-packet DHCP fast path on an already parsed frame (`parsed` is
+ * parse_pkt's result).  Returns verdict; *out_len set on TX. */
+BNG_DEV int dhcp_process_ctx(pktctx& c, bool parsed, int stride,
+                             const dhcp_tables& T, dhcp_flags& F,
+                             uint16_t* out_len) {
+  uint8_t* p = c.p;
+  const int len = c.len;
   *out_len = (uint16_t)len;
-  pktctx c;
-  if (!parse_pkt(c, p, len, /*want_vlan=*/true)) {
+  if (!parsed) {
     if (c.tagged) F.vlan = true;
     return BNG_PASS;
   }
@@ -568,8 +725,30 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
   if (c.dport != 67) return BNG_PASS;
   int dhcp_off = c.l4_off + 8;
   if (len < dhcp_off + 240) return BNG_PASS;
-  if (p[dhcp_off] != 1) return BNG_PASS;               /* BOOTREQUEST */
-  if (ld_u32be(p + dhcp_off + 236) != 0x63825363u) return BNG_PASS;
+  /* wide: constant offsets, row long enough for the longest reply */
+  const bool wide = c.regs && stride >= BNG_DHCP_WIDE_MIN_STRIDE;
+  uint32_t X[12];                    /* bytes 48..95 when wide */
+  #pragma unroll
+  for (int i = 0; i < 12; ++i) X[i] = 0;
+  if (wide) {
+    if (RG_B(c, 42) != 1) return BNG_PASS;             /* BOOTREQUEST */
+    const uint4* q = (const uint4*)p;
+    uint4 m = q[17];                 /* 272..287: cookie at 278..281 */
+    uint32_t cookie = (__builtin_bswap32(m.y) << 16) |
+                      (__builtin_bswap32(m.z) >> 16);
+    if (cookie != 0x63825363u) return BNG_PASS;
+    #pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      uint4 v = q[3 + i];
+      X[i * 4 + 0] = __builtin_bswap32(v.x);
+      X[i * 4 + 1] = __builtin_bswap32(v.y);
+      X[i * 4 + 2] = __builtin_bswap32(v.z);
+      X[i * 4 + 3] = __builtin_bswap32(v.w);
+    }
+  } else {
+    if (p[dhcp_off] != 1) return BNG_PASS;             /* BOOTREQUEST */
+    if (ld_u32be(p + dhcp_off + 236) != 0x63825363u) return BNG_PASS;
+  }
 
   F.total = true;
 
@@ -584,17 +763,25 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
     sub = sub_lookup(T.subs, T.sub_mask, vk);
   }
   if (!sub && cid) {
-    uint8_t padded[32];
-    #pragma unroll
-    for (int i = 0; i < 32; ++i) padded[i] = (i < cid_len) ? cid[i] : 0;
-    uint64_t ck = BNG_KEY_CIRCUIT | (bng_fnv1a64(padded, 32) >> 2);
+    /* FNV-1a over the circuit-id zero-padded to 32 bytes, hashed as it
+     * is read (a padded copy would live in scratch memory) */
+    uint64_t h = 0xCBF29CE484222325ULL;
+    for (int i = 0; i < 32; ++i) {
+      h ^= (i < cid_len) ? cid[i] : 0;
+      h *= 0x100000001B3ULL;
+    }
+    uint64_t ck = BNG_KEY_CIRCUIT | (h >> 2);
     sub = sub_lookup(T.subs, T.sub_mask, ck);
     if (sub) F.o82 = true;
   }
   if (!sub) {
     uint64_t mac = 0;
-    #pragma unroll
-    for (int i = 0; i < 6; ++i) mac = (mac << 8) | p[dhcp_off + 28 + i];
+    if (wide) {
+      mac = ((uint64_t)w_ld16(X, 70 - 48) << 32) | w_ld32(X, 72 - 48);
+    } else {
+      #pragma unroll
+      for (int i = 0; i < 6; ++i) mac = (mac << 8) | p[dhcp_off + 28 + i];
+    }
     sub = sub_lookup(T.subs, T.sub_mask, mac);
   }
   if (!sub) { F.miss = true; return BNG_PASS; }
@@ -606,10 +793,16 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
 
   const bng_server_config cfg = *T.cfg;
   uint8_t reply_type = (msg_type == 1) ? 2 : 5;     /* OFFER : ACK */
-  uint32_t giaddr = ld_u32be(p + dhcp_off + 24);
   /* table IPs are stored as host ints equal to their wire (big-endian)
    * interpretation — the same values ip2u32()/ld_u32be() produce */
   uint32_t server_ip = cfg.server_ip ? cfg.server_ip : pool.gateway;
+  if (wide) {
+    dhcp_reply R{sub->allocated_ip, server_ip, reply_type};
+    int total = dhcp_reply_wide(c, X, R, pool, cfg, F);
+    *out_len = (uint16_t)min(total, stride);
+    return BNG_TX;
+  }
+  uint32_t giaddr = ld_u32be(p + dhcp_off + 24);
 
   int ip_off = c.ip_off, udp_off = c.l4_off;
   if (giaddr != 0) {   /* relayed: unicast to relay agent (ref :726-743) */
@@ -655,10 +848,7 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
   o[w++] = 53; o[w++] = 1; o[w++] = reply_type;
   o[w++] = 54; o[w++] = 4; st_u32be(o + w, server_ip); w += 4;
   o[w++] = 51; o[w++] = 4; st_u32be(o + w, pool.lease_time); w += 4;
-  uint32_t mask32 = (pool.prefix_len == 0) ? 0
-      : (pool.prefix_len >= 32) ? 0xFFFFFFFFu
-      : (0xFFFFFFFFu << (32 - pool.prefix_len));
-  o[w++] = 1;  o[w++] = 4; st_u32be(o + w, mask32); w += 4;
+  o[w++] = 1;  o[w++] = 4; st_u32be(o + w, pool_netmask(pool)); w += 4;
   o[w++] = 3;  o[w++] = 4; st_u32be(o + w, pool.gateway); w += 4;
   if (pool.dns_primary) {
     uint8_t dl = pool.dns_secondary ? 8 : 4;
@@ -686,6 +876,15 @@ BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
 
   *out_len = (uint16_t)min(total, stride);
   return BNG_TX;
+}
+
+/* parse + process, for the kernels that see nothing but DHCP */
+BNG_DEV int dhcp_process(uint8_t* p, int len, int stride,
+                         const dhcp_tables& T, dhcp_flags& F,
+                         uint16_t* out_len) {
+  pktctx c;
+  bool parsed = parse_pkt(c, p, len, /*want_vlan=*/true);
+  return dhcp_process_ctx(c, parsed, stride, T, F, out_len);
 }
 
 /* Layout of the per-block shared counter array the batched packet kernels
@@ -1643,9 +1842,14 @@ __global__ void antispoof_kernel(
 /* One pass per packet over the chain the reference runs as four separate
  * kernel hooks: DHCP fast path for UDP:67, else antispoof -> NAT44 SNAT
  * -> QoS ingress.  One parse, one packet-data round trip — the fusion the
- * CDNA4 guide prescribes for HBM-bound pipelines. */
-__global__ __launch_bounds__(256, 5)  /* cap VGPRs at 96 -> 5 waves/SIMD:
-    the pipeline is latency-bound (SQ_WAIT ~95%), occupancy is the lever */
+ * CDNA4 guide prescribes for HBM-bound pipelines.
+ *
+ * Register budget: the default grid (512 blocks of 4 waves on 256 CUs)
+ * keeps two waves per SIMD resident, so the bound asks for no more than
+ * that.  A tighter cap (5 waves, 96 VGPRs) bought no occupancy the grid
+ * ever used and forced 35 VGPR spills into the per-packet loop, whose
+ * scratch traffic shares the memory pipe with the table probes. */
+__global__ __launch_bounds__(256, 2)
 void uplink_pipeline_kernel(bng_uplink_params P) {
   if (P.now_ptr) { P.now_ns = P.now_ptr[0]; P.now_sec = P.now_ptr[1]; }
   dhcp_tables DT{P.subs, P.sub_mask, P.pools, P.n_pools, P.scfg,
@@ -1693,7 +1897,7 @@ void uplink_pipeline_kernel(bng_uplink_params P) {
       bool is_dhcp = ip_ok && c.ip_off >= 0 && c.proto == 17 && c.l4_ok &&
                      c.dport == 67;
       if (is_dhcp) {
-        v = dhcp_process(p, len, P.stride, DT, DF, &ol);
+        v = dhcp_process_ctx(c, true, P.stride, DT, DF, &ol);
       } else if (ip_ok && !c.tagged && len >= 14) {
         /* hot data path: the two independent first-probe loads
          * (binding / merged subscriber context) issue together; the
