@@ -644,6 +644,14 @@ class BNG:
             self.accounting = AccountingManager(self.radius).start()
             self._defer(self.accounting.stop)
             self.dhcp_server.set_accounting(self.accounting)
+            # per-subscriber octet/packet counters from the dataplane
+            # (device tables, or the golden model with --gpu off)
+            from ..accounting.traffic import TrafficAccounting
+            self.traffic_accounting = TrafficAccounting(self.launcher)
+            self.dhcp_server.on_lease_event.append(
+                self.traffic_accounting.on_lease_event)
+            self.accounting.set_counter_fetcher(
+                self.traffic_accounting.fetch)
             if a.radius_coa_port:
                 from ..radius.coa import CoAProcessor, CoAServer
                 proc = CoAProcessor(

@@ -17,6 +17,7 @@ MAX_EIM_LOG2 = 22
 MAX_SUBNAT_LOG2 = 21
 MAX_QOS_LOG2 = 21
 MAX_BINDINGS_LOG2 = 21
+MAX_ACCT_LOG2 = 21
 MAX_PROBE = 128
 MAX_PRIVATE_RANGES = 64
 MAX_ALLOWED_RANGES = 256
@@ -296,6 +297,29 @@ class PppoeIp(C.Structure):
     _fields_ = [("key", C.c_uint64), ("sid_mac", C.c_uint64)]
 
 
+class AcctEntry(C.Structure):
+    """Per-subscriber traffic counters, keyed by acct_key(ip)."""
+    _fields_ = [("key", C.c_uint64), ("up_bytes", C.c_uint64),
+                ("up_pkts", C.c_uint64), ("down_bytes", C.c_uint64),
+                ("down_pkts", C.c_uint64), ("up_drop_pkts", C.c_uint64),
+                ("down_drop_pkts", C.c_uint64), ("last_seen", C.c_uint64)]
+
+
+# bng_acct_entry as a numpy record (acct_read / acct_remove / acct_export);
+# field names and offsets are AcctEntry's
+ACCT_ENTRY_DTYPE = [("key", "<u8"), ("up_bytes", "<u8"), ("up_pkts", "<u8"),
+                    ("down_bytes", "<u8"), ("down_pkts", "<u8"),
+                    ("up_drop_pkts", "<u8"), ("down_drop_pkts", "<u8"),
+                    ("last_seen", "<u8")]
+ACCT_COUNTERS = [f[0] for f in ACCT_ENTRY_DTYPE[1:]]
+
+
+def acct_key(ip: int) -> int:
+    """Accounting table key; bit 32 keeps it clear of EMPTY and TOMBSTONE
+    for any address."""
+    return (1 << 32) | (ip & 0xFFFFFFFF)
+
+
 EXPECTED_SIZES = {
     "bng_sub_entry": (SubEntry, 32),
     "bng_ip_pool": (IpPool, 28),
@@ -316,6 +340,7 @@ EXPECTED_SIZES = {
     "bng_sess_export": (SessExport, 48),
     "bng_pppoe_sess": (PppoeSess, 16),
     "bng_pppoe_ip": (PppoeIp, 16),
+    "bng_acct_entry": (AcctEntry, 64),
 }
 
 

@@ -38,6 +38,7 @@ enum {
   BNG_MAX_SUBNAT_LOG2      = 21,
   BNG_MAX_QOS_LOG2         = 21,
   BNG_MAX_BINDINGS_LOG2    = 21,
+  BNG_MAX_ACCT_LOG2        = 21, /* 2M slots for 1M accounted subscribers  */
   BNG_MAX_PROBE            = 128, /* linear-probe bound before declaring full */
   BNG_MAX_PRIVATE_RANGES   = 64,  /* bpf/nat44.c:314-320 nat_private_ranges */
   BNG_MAX_ALLOWED_RANGES   = 256, /* bpf/antispoof.c:113-119 allowed_ranges_v4 */
@@ -374,6 +375,26 @@ enum bng_pppoe_state {
   BNG_PPPOE_TOO_BIG = 5, /* downlink: exceeds the peer MRU, verdict -> PASS   */
   BNG_PPPOE_NO_ROOM = 6, /* downlink: row too short for +8 B, verdict -> PASS */
 };
+
+/* ------------------------------------------- per-subscriber accounting */
+/* Traffic counters of one subscriber, the source of the RADIUS
+ * Acct-Input/Output-Octets/Packets (ref pkg/radius/client.go:289-304).
+ * One cache line per entry, keyed by the subscriber IPv4 (the integer
+ * ip2u32 yields and add_subscriber_nat takes).  Open addressing with the
+ * usual EMPTY / TOMBSTONE keys and BNG_MAX_PROBE bound.  Host-inserted
+ * (stream-ordered), device-updated with relaxed agent-scope atomics. */
+#define BNG_ACCT_KEY(ip) ((1ULL << 32) | (uint64_t)(uint32_t)(ip))  /* never 0 / ~0 */
+
+typedef struct bng_acct_entry {
+  uint64_t key;            /* BNG_ACCT_KEY(ip); 0 empty, ~0 tombstone          */
+  uint64_t up_bytes;       /* forwarded subscriber -> core                      */
+  uint64_t up_pkts;
+  uint64_t down_bytes;     /* forwarded core -> subscriber                      */
+  uint64_t down_pkts;
+  uint64_t up_drop_pkts;   /* verdict DROP (antispoof / NAT / QoS), uplink      */
+  uint64_t down_drop_pkts;
+  uint64_t last_seen;      /* batch now_ns of the last FORWARDED packet         */
+} bng_acct_entry;  /* 64 B */
 
 /* ----------------------------------------------------------- ring header */
 /* Device->host ordered log ring: device atomically bumps widx; host reads

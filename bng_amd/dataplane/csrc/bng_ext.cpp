@@ -454,6 +454,122 @@ void pppoe_sess_delete(torch::Tensor sess, torch::Tensor by_ip,
       sids.data_ptr(), n, cur_stream());
 }
 
+/* Per-subscriber traffic accounting.  The packet kernels read rows with
+ * 16-B loads up to byte 47, the commit indexes slot / verdict / out_len by
+ * packet id and the table by slot, so every size is checked here. */
+uint32_t acct_table_mask(const torch::Tensor& table) {
+  return dev_table_mask(table, sizeof(bng_acct_entry), "acct");
+}
+
+void check_acct_batch(const torch::Tensor& data,
+                      const torch::Tensor& in_len) {
+  check_dev(data, "data"); check_dev(in_len, "in_len");
+  TORCH_CHECK(data.dim() == 2 && data.element_size() == 1,
+              "data must be [n, stride] bytes");
+  TORCH_CHECK(data.size(0) == in_len.numel() && in_len.element_size() == 2,
+              "in_len must hold one 16-bit length per row");
+  TORCH_CHECK(data.size(1) >= 64 && data.size(1) % 16 == 0 &&
+              data.size(1) <= 65535,
+              "accounting needs a stride that is a multiple of 16, "
+              "64..65535");
+  TORCH_CHECK(((uintptr_t)data.data_ptr() & 15) == 0,
+              "accounting needs a 16-byte aligned batch");
+}
+
+void acct_resolve(torch::Tensor data, torch::Tensor in_len,
+                  torch::Tensor slot, torch::Tensor table) {
+  check_acct_batch(data, in_len);
+  check_dev(slot, "slot");
+  TORCH_CHECK(slot.element_size() == 4 && slot.numel() >= in_len.numel(),
+              "slot must hold one int32 per row");
+  uint32_t mask = acct_table_mask(table);
+  int n = (int)in_len.numel();
+  if (n == 0) return;
+  bng_launch_acct_resolve(data.data_ptr(), in_len.data_ptr(),
+                          slot.data_ptr(), n, (int)data.size(1),
+                          table.data_ptr(), mask, cur_stream());
+}
+
+void acct_commit(torch::Tensor table, torch::Tensor slot,
+                 torch::Tensor verdict, torch::Tensor out_len,
+                 int64_t now_ns) {
+  check_dev(slot, "slot"); check_dev(verdict, "verdict");
+  check_dev(out_len, "out_len");
+  int64_t n = verdict.numel();
+  TORCH_CHECK(n <= INT_MAX, "batch too large");
+  TORCH_CHECK(verdict.element_size() == 1, "verdict must be bytes");
+  TORCH_CHECK(slot.element_size() == 4 && slot.numel() >= n,
+              "slot must hold one int32 per row");
+  TORCH_CHECK(out_len.element_size() == 2 && out_len.numel() == n,
+              "out_len must hold one 16-bit length per row");
+  uint32_t mask = acct_table_mask(table);
+  if (n == 0) return;
+  bng_launch_acct_commit(table.data_ptr(), mask, slot.data_ptr(),
+                         verdict.data_ptr(), out_len.data_ptr(), (int)n,
+                         (uint64_t)now_ns, cur_stream());
+}
+
+void acct_downlink(torch::Tensor data, torch::Tensor in_len,
+                   torch::Tensor verdict, torch::Tensor table,
+                   int64_t now_ns) {
+  check_acct_batch(data, in_len);
+  check_dev(verdict, "verdict");
+  TORCH_CHECK(verdict.numel() == in_len.numel() &&
+              verdict.element_size() == 1,
+              "verdict must hold one byte per row");
+  uint32_t mask = acct_table_mask(table);
+  int n = (int)in_len.numel();
+  if (n == 0) return;
+  bng_launch_acct_downlink(data.data_ptr(), in_len.data_ptr(),
+                           verdict.data_ptr(), n, (int)data.size(1),
+                           table.data_ptr(), mask, (uint64_t)now_ns,
+                           cur_stream());
+}
+
+/* Checks the address list of an accounting CRUD call; returns its count. */
+int acct_ip_count(const torch::Tensor& ips) {
+  check_dev(ips, "ips");
+  TORCH_CHECK(ips.element_size() == 4, "ips must be 32-bit");
+  TORCH_CHECK(ips.numel() <= INT_MAX, "too many addresses");
+  return (int)ips.numel();
+}
+
+void acct_upsert(torch::Tensor table, torch::Tensor ips, bool reset,
+                 torch::Tensor rc) {
+  uint32_t mask = acct_table_mask(table);
+  int n = acct_ip_count(ips);
+  check_dev(rc, "rc");
+  TORCH_CHECK(rc.element_size() == 4 && rc.numel() >= n,
+              "rc must hold one int32 per address");
+  if (n == 0) return;
+  bng_launch_acct_upsert(table.data_ptr(), mask, ips.data_ptr(), n,
+                         reset ? 1 : 0, rc.data_ptr(), cur_stream());
+}
+
+void acct_read(torch::Tensor table, torch::Tensor ips, torch::Tensor out) {
+  uint32_t mask = acct_table_mask(table);
+  int n = acct_ip_count(ips);
+  check_dev(out, "out");
+  TORCH_CHECK(nbytes(out) >= (size_t)n * sizeof(bng_acct_entry) &&
+              ((uintptr_t)out.data_ptr() & 15) == 0,
+              "out must hold one 64-byte entry per address");
+  if (n == 0) return;
+  bng_launch_acct_read(table.data_ptr(), mask, ips.data_ptr(), n,
+                       out.data_ptr(), cur_stream());
+}
+
+void acct_delete(torch::Tensor table, torch::Tensor ips, torch::Tensor out) {
+  uint32_t mask = acct_table_mask(table);
+  int n = acct_ip_count(ips);
+  check_dev(out, "out");
+  TORCH_CHECK(nbytes(out) >= (size_t)n * sizeof(bng_acct_entry) &&
+              ((uintptr_t)out.data_ptr() & 15) == 0,
+              "out must hold one 64-byte entry per address");
+  if (n == 0) return;
+  bng_launch_acct_delete(table.data_ptr(), mask, ips.data_ptr(), n,
+                         out.data_ptr(), cur_stream());
+}
+
 /* Fine-grained-coherent pinned host memory for the persistent-service
  * doorbell/rings.  torch's pin_memory allocates COARSE-grained host
  * memory on ROCm: a running kernel caches it and never observes host
@@ -545,7 +661,7 @@ py::dict layout_report() {
   SZ(bng_nat_log_entry); SZ(bng_qos_bucket); SZ(bng_binding_entry);
   SZ(bng_antispoof_config); SZ(bng_spoof_event); SZ(bng_ring_header);
   SZ(bng_svc_ctrl); SZ(bng_sess_export);
-  SZ(bng_pppoe_sess); SZ(bng_pppoe_ip);
+  SZ(bng_pppoe_sess); SZ(bng_pppoe_ip); SZ(bng_acct_entry);
 #undef SZ
   py::dict off;
   off["sub_entry.lease_expiry"] = offsetof(bng_sub_entry, lease_expiry);
@@ -568,9 +684,23 @@ py::dict layout_report() {
   off["pppoe_sess.mru"] = offsetof(bng_pppoe_sess, mru);
   off["pppoe_sess.session_id"] = offsetof(bng_pppoe_sess, session_id);
   off["pppoe_ip.sid_mac"] = offsetof(bng_pppoe_ip, sid_mac);
+  off["acct_entry.up_bytes"] = offsetof(bng_acct_entry, up_bytes);
+  off["acct_entry.down_bytes"] = offsetof(bng_acct_entry, down_bytes);
+  off["acct_entry.up_drop_pkts"] = offsetof(bng_acct_entry, up_drop_pkts);
+  off["acct_entry.last_seen"] = offsetof(bng_acct_entry, last_seen);
   d["offsets"] = off;
   return d;
 }
+
+/* Peel rounds of the accounting commit's wave-level combining: 0 = none,
+ * < 0 = until nothing is pending.  The A/B knob of scripts/acct_bench.py;
+ * tests use it to run every variant over the same batches. */
+void set_acct_combine(int64_t rounds) {
+  TORCH_CHECK(rounds >= -1 && rounds <= 64, "rounds in [-1,64]");
+  bng_set_acct_combine((int)rounds);
+}
+
+int64_t get_acct_combine() { return bng_get_acct_combine(); }
 
 /* Grid cap (in 256-thread blocks) of the batched packet kernels; 0
  * restores the built-in default.  The A/B knob for grid sizing, and the
@@ -621,6 +751,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pppoe_encap", &pppoe_encap);
   m.def("pppoe_sess_upsert", &pppoe_sess_upsert);
   m.def("pppoe_sess_delete", &pppoe_sess_delete);
+  m.def("acct_resolve", &acct_resolve);
+  m.def("acct_commit", &acct_commit);
+  m.def("acct_downlink", &acct_downlink);
+  m.def("acct_upsert", &acct_upsert);
+  m.def("acct_read", &acct_read);
+  m.def("acct_delete", &acct_delete);
+  m.def("set_acct_combine", &set_acct_combine, py::arg("rounds"));
+  m.def("get_acct_combine", &get_acct_combine);
   m.def("nat_sweep", &nat_sweep);
   m.def("shard_owner", &shard_owner);
   m.def("dhcp_service_start", &dhcp_service_start);

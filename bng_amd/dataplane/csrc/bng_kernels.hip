@@ -2542,6 +2542,237 @@ __global__ void pppoe_sess_delete_kernel(bng_pppoe_sess* sess,
   sess[sid] = bng_pppoe_sess{0, 0, 0, 0};
 }
 
+/* ==================================== per-subscriber traffic accounting */
+/* Billing counts forwarded bytes and packets per subscriber, so accounting
+ * must know the verdict, and on the uplink it must key on the source
+ * address that SNAT overwrites.  Like PPPoE it therefore lives in small
+ * kernels around the fused pipelines instead of inside them (the uplink
+ * kernel has no registers to spare): acct_resolve_kernel ahead of the
+ * uplink pipeline turns the source address into a table slot,
+ * acct_commit_kernel behind it adds what the verdict says, and
+ * acct_downlink_kernel does both behind the downlink pipeline, on the
+ * DNAT-rewritten destination.  None is launched while no entry is live.
+ *
+ * Rows are 16-B aligned (the extension checks), so the frame is read with
+ * the 16-B window loads of the PPPoE kernels; the commit reads no packet
+ * bytes at all. */
+
+/* Slot of the entry of an untagged IPv4 frame's source (or destination)
+ * address, or -1: not IPv4, too short, or nobody accounts that address. */
+template <bool BY_DST>
+BNG_DEV int acct_resolve(const bng_acct_entry* __restrict__ t, uint32_t mask,
+                         const uint8_t* p, int len, int stride) {
+  if (len < 34) return -1;
+  uint4 h0 = *(const uint4*)p;                       /* bytes 0..15  */
+  if ((h0.w & 0xFFFFu) != 0x0008u) return -1;        /* 08 00 */
+  uint4 h1 = *(const uint4*)(p + 16);                /* bytes 16..31 */
+  uint32_t ip;
+  if (BY_DST) {
+    uint4 h2 = row_ld16(p, 32, stride);              /* bytes 32..47 */
+    ip = __builtin_bswap32((h1.w >> 16) | (h2.x << 16));   /* 30..33 */
+  } else {
+    ip = __builtin_bswap32((h1.z >> 16) | (h1.w << 16));   /* 26..29 */
+  }
+  uint64_t key = BNG_ACCT_KEY(ip);
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+    uint32_t s = (slot + i) & mask;
+    uint4 e = ld_probe16(&t[s]);
+    uint64_t k = ((uint64_t)e.y << 32) | e.x;
+    if (k == key) return (int)s;
+    if (k == BNG_KEY_EMPTY) return -1;
+  }
+  return -1;
+}
+
+BNG_DEV void acct_add64(uint64_t* p, uint64_t v) {
+  /* result unused: a no-return global atomic */
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* One entry's adds: `fwd` forwarded packets of `bytes` in total, `drop`
+ * dropped ones.  last_seen needs no max: batches are stream-ordered and
+ * every writer of a batch stores the same now_ns. */
+template <bool DOWN>
+BNG_DEV void acct_issue(bng_acct_entry* e, uint32_t fwd, uint32_t bytes,
+                        uint32_t drop, uint64_t now_ns) {
+  if (fwd) {
+    acct_add64(DOWN ? &e->down_pkts : &e->up_pkts, fwd);
+    acct_add64(DOWN ? &e->down_bytes : &e->up_bytes, bytes);
+    rlx_store64(&e->last_seen, now_ns);
+  }
+  if (drop) acct_add64(DOWN ? &e->down_drop_pkts : &e->up_drop_pkts, drop);
+}
+
+/* Wave-level commit.  Subscriber traffic is heavy-tailed: one busy
+ * subscriber can own most lanes of a wave, and 64 lanes adding to one
+ * cache line serialise at the memory side.  So up to `rounds` times the
+ * wave peels the group of the first pending lane — all pending lanes with
+ * that lane's slot — sums the group and lets its first lane issue the
+ * adds.  A round that finds a group of one ends the peeling (the wave then
+ * looks like distinct subscribers, where peeling is pure overhead), and
+ * whatever is still pending after the rounds goes out as per-lane atomics.
+ * rounds = 0: no combining; rounds < 0: peel until nothing is pending.
+ * Exact for every distribution of slots over lanes: a lane leaves
+ * `pending` only when its group's sum has been issued.
+ *
+ * Must be reached by every lane of the wave (ballots, readlane, shuffles):
+ * lanes with nothing to add pass slot = -1.  `bytes` <= 65535 per lane, so
+ * a wave's sum fits 32 bits. */
+template <bool DOWN>
+BNG_DEV void acct_commit_wave(bng_acct_entry* t, int slot, bool fwd,
+                              bool drop, uint32_t bytes, uint64_t now_ns,
+                              int rounds) {
+  bool pending = slot >= 0 && (fwd || drop);
+  if (!fwd) bytes = 0;
+  int lane = threadIdx.x & 63;
+  for (int r = 0; rounds < 0 || r < rounds; ++r) {
+    unsigned long long m = __ballot(pending);
+    if (m == 0) break;                       /* wave-uniform */
+    int first = __ffsll(m) - 1;
+    int gslot = __builtin_amdgcn_readlane(slot, first);
+    bool mine = pending && slot == gslot;
+    unsigned long long g = __ballot(mine);
+    if ((g & (g - 1)) == 0) break;           /* a group of one: stop */
+    uint32_t nf = wave_count(mine && fwd);
+    uint32_t nd = wave_count(mine && drop);
+    uint32_t nb = wave_sum32(mine ? bytes : 0u);
+    if (lane == first) acct_issue<DOWN>(&t[gslot], nf, nb, nd, now_ns);
+    pending = pending && !mine;
+  }
+  if (pending)
+    acct_issue<DOWN>(&t[slot], fwd ? 1u : 0u, bytes, drop ? 1u : 0u, now_ns);
+}
+
+/* Uplink pre-pass: after pppoe_decap, before the pipeline.  slot[] is
+ * indexed by packet id, like verdict[], so a sorted dispatch order of the
+ * pipeline between the two passes changes nothing. */
+__global__ __launch_bounds__(256)
+void acct_resolve_kernel(const uint8_t* __restrict__ data,
+                         const uint16_t* __restrict__ in_len,
+                         int32_t* __restrict__ slot, int n, int stride,
+                         const bng_acct_entry* __restrict__ t,
+                         uint32_t mask) {
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int pid = tid; pid < n; pid += nthreads)
+    slot[pid] = acct_resolve<false>(t, mask, data + (size_t)pid * stride,
+                                    in_len[pid], stride);
+}
+
+/* Uplink post-pass: after the pipeline and the launcher's PPPoE-reject
+ * fill.  Reads slot[], verdict[] and out_len[] only.  FWD is billed, DROP
+ * is counted, PASS and TX (a DHCP reply is not subscriber traffic) count
+ * nothing.  No lane leaves an iteration early: every lane of a wave
+ * reaches acct_commit_wave, lanes past n with slot -1. */
+__global__ __launch_bounds__(256)
+void acct_commit_kernel(bng_acct_entry* t, uint32_t mask,
+                        const int32_t* __restrict__ slot,
+                        const uint8_t* __restrict__ verdict,
+                        const uint16_t* __restrict__ out_len, int n,
+                        uint64_t now_ns, int rounds) {
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int pid = base + tid;
+    int s = -1;
+    bool fwd = false, drop = false;
+    uint32_t bytes = 0;
+    if (pid < n) do {
+      s = slot[pid];
+      if ((uint32_t)s > mask) { s = -1; break; }     /* -1, or defensive */
+      uint8_t v = verdict[pid];
+      fwd = v == BNG_FWD;
+      drop = v == BNG_DROP;
+      bytes = out_len[pid];
+    } while (0);
+    acct_commit_wave<false>(t, s, fwd, drop, bytes, now_ns, rounds);
+  }
+}
+
+/* Downlink post-pass: after the pipeline, before pppoe_encap, so both
+ * directions count the IPoE frame length.  Resolves on the DNAT-rewritten
+ * destination — a frame NAT dropped for lack of a session still carries
+ * the public address, resolves to nothing and is not counted — and commits
+ * in the same launch. */
+__global__ __launch_bounds__(256)
+void acct_downlink_kernel(const uint8_t* __restrict__ data,
+                          const uint16_t* __restrict__ in_len,
+                          const uint8_t* __restrict__ verdict, int n,
+                          int stride, bng_acct_entry* t, uint32_t mask,
+                          uint64_t now_ns, int rounds) {
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int pid = base + tid;
+    int s = -1;
+    bool fwd = false, drop = false;
+    uint32_t bytes = 0;
+    if (pid < n) do {
+      uint8_t v = verdict[pid];
+      fwd = v == BNG_FWD;
+      drop = v == BNG_DROP;
+      if (!fwd && !drop) break;
+      bytes = in_len[pid];
+      s = acct_resolve<true>(t, mask, data + (size_t)pid * stride,
+                             (int)bytes, stride);
+    } while (0);
+    acct_commit_wave<true>(t, s, fwd, drop, bytes, now_ns, rounds);
+  }
+}
+
+/* Stream-ordered entry CRUD, one thread per batch record, under the batch
+ * contract of the host CRUD probes: a batch must not name the same address
+ * twice. */
+__global__ void acct_upsert_kernel(bng_acct_entry* t, uint32_t mask,
+                                   const uint32_t* __restrict__ ips, int n,
+                                   int reset, int* rc) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t key = BNG_ACCT_KEY(ips[i]);
+  bool existed = key_find<&bng_acct_entry::key>(t, mask, key) != nullptr;
+  bng_acct_entry* e = key_upsert_slot<&bng_acct_entry::key>(t, mask, key);
+  if (!e) { rc[i] = -1; return; }
+  /* a fresh claim may sit on a tombstone that still holds the previous
+   * owner's counters */
+  if (!existed || reset) {
+    e->up_bytes = 0; e->up_pkts = 0; e->down_bytes = 0; e->down_pkts = 0;
+    e->up_drop_pkts = 0; e->down_drop_pkts = 0; e->last_seen = 0;
+  }
+  rc[i] = 0;
+}
+
+BNG_DEV void acct_copy_out(bng_acct_entry* out, const bng_acct_entry* e) {
+  uint4* o = (uint4*)out;
+  const uint4* s = (const uint4*)e;
+  uint4 z = make_uint4(0, 0, 0, 0);
+  #pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = e ? s[k] : z;   /* absent: key == 0 */
+}
+
+__global__ void acct_read_kernel(bng_acct_entry* t, uint32_t mask,
+                                 const uint32_t* __restrict__ ips, int n,
+                                 bng_acct_entry* out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  acct_copy_out(&out[i], key_find<&bng_acct_entry::key>(
+      t, mask, BNG_ACCT_KEY(ips[i])));
+}
+
+/* The final counters for the Stop record: copy, then tombstone, in one
+ * stream-ordered step no packet kernel can fall between. */
+__global__ void acct_delete_kernel(bng_acct_entry* t, uint32_t mask,
+                                   const uint32_t* __restrict__ ips, int n,
+                                   bng_acct_entry* out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bng_acct_entry* e =
+      key_find<&bng_acct_entry::key>(t, mask, BNG_ACCT_KEY(ips[i]));
+  acct_copy_out(&out[i], e);
+  if (e) rlx_store64(&e->key, BNG_KEY_TOMBSTONE);
+}
+
 /* ============================= extern "C" launchers for the extension */
 
 /* Grid cap of the six batched packet kernels (grid-stride above it).
@@ -2559,6 +2790,13 @@ static inline int pkt_grid(int n) {
   int blocks = (n + 255) / 256;
   return blocks < g_pkt_grid_cap ? blocks : g_pkt_grid_cap;
 }
+
+/* Peel rounds of the accounting commit (acct_commit_wave): 0 = per-lane
+ * atomics only, < 0 = peel until nothing is pending.  The default is the
+ * variant profiles/ACCOUNTING.md picks; bng_set_acct_combine() overrides
+ * it for A/B runs and tests. */
+#define BNG_ACCT_ROUNDS_DEFAULT 4
+static int g_acct_rounds = BNG_ACCT_ROUNDS_DEFAULT;
 
 /* classify / shard-owner helpers keep their own fixed cap */
 static inline int aux_grid(int n) {
@@ -2749,6 +2987,58 @@ void bng_launch_pppoe_sess_delete(void* sess, void* by_ip, uint32_t ip_mask,
   hipLaunchKernelGGL(pppoe_sess_delete_kernel, dim3((n + 255) / 256),
       dim3(256), 0, s, (bng_pppoe_sess*)sess, (bng_pppoe_ip*)by_ip, ip_mask,
       (const int32_t*)sids, n);
+}
+
+void bng_set_acct_combine(int rounds) { g_acct_rounds = rounds; }
+int bng_get_acct_combine(void) { return g_acct_rounds; }
+
+void bng_launch_acct_resolve(const void* data, const void* in_len,
+                             void* slot, int n, int stride,
+                             const void* table, uint32_t mask,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(acct_resolve_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (const uint8_t*)data, (const uint16_t*)in_len, (int32_t*)slot, n,
+      stride, (const bng_acct_entry*)table, mask);
+}
+
+void bng_launch_acct_commit(void* table, uint32_t mask, const void* slot,
+                            const void* verdict, const void* out_len, int n,
+                            uint64_t now_ns, hipStream_t s) {
+  hipLaunchKernelGGL(acct_commit_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (bng_acct_entry*)table, mask, (const int32_t*)slot,
+      (const uint8_t*)verdict, (const uint16_t*)out_len, n, now_ns,
+      g_acct_rounds);
+}
+
+void bng_launch_acct_downlink(const void* data, const void* in_len,
+                              const void* verdict, int n, int stride,
+                              void* table, uint32_t mask, uint64_t now_ns,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(acct_downlink_kernel, dim3(pkt_grid(n)), dim3(256), 0,
+      s, (const uint8_t*)data, (const uint16_t*)in_len,
+      (const uint8_t*)verdict, n, stride, (bng_acct_entry*)table, mask,
+      now_ns, g_acct_rounds);
+}
+
+void bng_launch_acct_upsert(void* table, uint32_t mask, const void* ips,
+                            int n, int reset, void* rc, hipStream_t s) {
+  hipLaunchKernelGGL(acct_upsert_kernel, dim3((n + 255) / 256), dim3(256), 0,
+      s, (bng_acct_entry*)table, mask, (const uint32_t*)ips, n, reset,
+      (int*)rc);
+}
+
+void bng_launch_acct_read(void* table, uint32_t mask, const void* ips, int n,
+                          void* out, hipStream_t s) {
+  hipLaunchKernelGGL(acct_read_kernel, dim3((n + 255) / 256), dim3(256), 0,
+      s, (bng_acct_entry*)table, mask, (const uint32_t*)ips, n,
+      (bng_acct_entry*)out);
+}
+
+void bng_launch_acct_delete(void* table, uint32_t mask, const void* ips,
+                            int n, void* out, hipStream_t s) {
+  hipLaunchKernelGGL(acct_delete_kernel, dim3((n + 255) / 256), dim3(256), 0,
+      s, (bng_acct_entry*)table, mask, (const uint32_t*)ips, n,
+      (bng_acct_entry*)out);
 }
 
 void bng_launch_shard_owner(const void* data, const void* in_len,

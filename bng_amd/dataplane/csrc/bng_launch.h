@@ -69,6 +69,23 @@ void bng_launch_pppoe_sess_upsert(void* sess, void* by_ip, uint32_t ip_mask,
     const void* batch, int n, void* rc, hipStream_t s);
 void bng_launch_pppoe_sess_delete(void* sess, void* by_ip, uint32_t ip_mask,
     const void* sids, int n, hipStream_t s);
+void bng_set_acct_combine(int rounds);
+int bng_get_acct_combine(void);
+void bng_launch_acct_resolve(const void* data, const void* in_len,
+    void* slot, int n, int stride, const void* table, uint32_t mask,
+    hipStream_t s);
+void bng_launch_acct_commit(void* table, uint32_t mask, const void* slot,
+    const void* verdict, const void* out_len, int n, uint64_t now_ns,
+    hipStream_t s);
+void bng_launch_acct_downlink(const void* data, const void* in_len,
+    const void* verdict, int n, int stride, void* table, uint32_t mask,
+    uint64_t now_ns, hipStream_t s);
+void bng_launch_acct_upsert(void* table, uint32_t mask, const void* ips,
+    int n, int reset, void* rc, hipStream_t s);
+void bng_launch_acct_read(void* table, uint32_t mask, const void* ips, int n,
+    void* out, hipStream_t s);
+void bng_launch_acct_delete(void* table, uint32_t mask, const void* ips,
+    int n, void* out, hipStream_t s);
 
 } /* extern "C" */
 

@@ -121,6 +121,18 @@ class PppoeSessRec:
     mru: int = 1492
 
 
+@dataclass
+class AcctRec:
+    """Per-subscriber traffic counters (bng_acct_entry without its key)."""
+    up_bytes: int = 0
+    up_pkts: int = 0
+    down_bytes: int = 0
+    down_pkts: int = 0
+    up_drop_pkts: int = 0
+    down_drop_pkts: int = 0
+    last_seen: int = 0
+
+
 DEFAULT_PRIVATE_RANGES = [
     # is_private_ip inline ranges, ref nat44.c:340-363
     (0x0A000000, 0xFF000000),                    # 10.0.0.0/8
@@ -167,6 +179,8 @@ class GoldenDataplane:
         self.pppoe_sessions: Dict[int, PppoeSessRec] = {}   # by session id
         self.pppoe_by_ip: Dict[int, Tuple[int, int]] = {}   # ip -> (sid, mac)
         self.pppoe_stats = [0] * abi.PPPOE_NSTATS
+        # per-subscriber traffic accounting, by subscriber IPv4
+        self.acct: Dict[int, AcctRec] = {}
 
     # ------------------------------------------------------------- helpers
     @property
@@ -762,6 +776,42 @@ class GoldenDataplane:
                                    0x0021))
         self.pppoe_stats[abi.PS_ENCAP_OK] += 1
         return abi.PPPOE_ENCAP, verdict, n + 8
+
+    # ===================================== per-subscriber accounting
+    def acct_resolve(self, frame, by: str = "src") -> Optional[int]:
+        """The accounted address of an untagged IPv4 frame — its source
+        (uplink, BEFORE the pipeline: SNAT overwrites it) or destination
+        (downlink, AFTER the pipeline: DNAT has restored it) — or None:
+        not untagged IPv4, too short, or nobody accounts that address
+        (acct_resolve_kernel / acct_downlink_kernel)."""
+        if len(frame) < 34 or \
+                struct.unpack_from(">H", frame, 12)[0] != ETH_P_IP:
+            return None
+        ip = struct.unpack_from(">I", frame, 26 if by == "src" else 30)[0]
+        return ip if ip in self.acct else None
+
+    def acct_commit(self, key: Optional[int], direction: str, length: int,
+                    verdict: int, now_ns: int):
+        """Bill one packet to acct_resolve's key: FWD adds (1, length) and
+        stamps last_seen, DROP adds one dropped packet, PASS and TX count
+        nothing (acct_commit_kernel)."""
+        e = self.acct.get(key) if key is not None else None
+        if e is None:
+            return
+        up = direction == "uplink"
+        if verdict == FWD:
+            if up:
+                e.up_pkts += 1
+                e.up_bytes += length
+            else:
+                e.down_pkts += 1
+                e.down_bytes += length
+            e.last_seen = now_ns
+        elif verdict == DROP:
+            if up:
+                e.up_drop_pkts += 1
+            else:
+                e.down_drop_pkts += 1
 
     # ====================================================== antispoof K4
     def antispoof(self, frame: bytes) -> int:

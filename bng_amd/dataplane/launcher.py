@@ -47,7 +47,8 @@ class HipLauncher:
                  sub_log2: int = 18, sess_log2: int = 20, eim_log2: int = 19,
                  subnat_log2: int = 18, qos_log2: int = 18,
                  binding_log2: int = 18, n_pools: int = 1024,
-                 svc_cus: int = 0, pppoe_log2: int = 17):
+                 svc_cus: int = 0, pppoe_log2: int = 17,
+                 acct_log2: int = abi.MAX_ACCT_LOG2):
         import torch
         from .build import get_ext
         self.torch = torch
@@ -110,6 +111,16 @@ class HipLauncher:
         # downlink() launch exactly what they launched before PPPoE existed
         self._pppoe_live: Dict[int, Tuple[int, int]] = {}
         self.last_pppoe_state = None
+        # per-subscriber traffic accounting: the table (2^acct_log2 64-B
+        # entries) and the uplink's slot[] scratch exist from the first
+        # acct_add on; while no entry is live uplink() and downlink()
+        # launch exactly what they launched before accounting existed.
+        # acct_launches counts the accounting kernels they did launch.
+        self.acct_log2 = acct_log2
+        self.acct = None
+        self._acct_slot = None
+        self._acct_live: set = set()
+        self.acct_launches = {"resolve": 0, "commit": 0, "downlink": 0}
         # host-side circuit-id collision registry (ref loader.go:519-608)
         self._circuit_ids: Dict[int, bytes] = {}
         # defaults
@@ -442,6 +453,90 @@ class HipLauncher:
                              self.pppoe_stats)
         return state
 
+    # ===================================== per-subscriber accounting
+    def _acct_ips(self, ips):
+        import numpy as np
+        arr = np.asarray([int(ip) & 0xFFFFFFFF for ip in ips],
+                         dtype=np.uint32)
+        if len(set(arr.tolist())) != len(arr):
+            raise ValueError("an accounting batch must not repeat an address")
+        return arr, self.torch.from_numpy(arr.view(np.int32)).to(self.device)
+
+    def _acct_rows(self, out):
+        import numpy as np
+        return out.cpu().numpy().view(np.dtype(abi.ACCT_ENTRY_DTYPE)).copy()
+
+    def acct_add(self, ips, reset: bool = False):
+        """Start accounting the subscriber addresses `ips` (the integers
+        ip2u32 yields).  A new entry starts from zero; a live one keeps its
+        counters unless `reset`.  One launch; a batch must not repeat an
+        address."""
+        arr, dev = self._acct_ips(ips)
+        if not len(arr):
+            return
+        if self.acct is None:
+            self.acct = self.torch.zeros((1 << self.acct_log2) * 64,
+                                         dtype=self.torch.uint8,
+                                         device=self.device)
+            self._acct_slots(0)
+        rc = self.torch.zeros(len(arr), dtype=self.torch.int32,
+                              device=self.device)
+        self.ext.acct_upsert(self.acct, dev, bool(reset), rc)
+        # session start is a control-plane event: pay the sync and keep the
+        # host-side set of live entries exact
+        bad = (rc != 0).cpu().numpy()
+        self._acct_live.update(int(ip) for ip, failed in zip(arr, bad)
+                               if not failed)
+        if bad.any():
+            raise RuntimeError(
+                f"accounting table full: {int(bad.sum())} subscriber(s) not "
+                f"accounted (raise acct_log2, now {self.acct_log2})")
+
+    def acct_read(self, ips):
+        """Entries of the named addresses as ACCT_ENTRY_DTYPE records; an
+        address nobody accounts gives an all-zero row (key == 0)."""
+        import numpy as np
+        arr, dev = self._acct_ips(ips)
+        if self.acct is None or not len(arr):
+            return np.zeros(len(arr), dtype=abi.ACCT_ENTRY_DTYPE)
+        out = self.torch.zeros(len(arr) * 64, dtype=self.torch.uint8,
+                               device=self.device)
+        self.ext.acct_read(self.acct, dev, out)
+        return self._acct_rows(out)
+
+    def acct_remove(self, ips):
+        """Stop accounting `ips`; returns their final entries (the Stop
+        record's counters), read and removed in one stream-ordered step."""
+        import numpy as np
+        arr, dev = self._acct_ips(ips)
+        if self.acct is None or not len(arr):
+            return np.zeros(len(arr), dtype=abi.ACCT_ENTRY_DTYPE)
+        out = self.torch.zeros(len(arr) * 64, dtype=self.torch.uint8,
+                               device=self.device)
+        self.ext.acct_delete(self.acct, dev, out)
+        self._acct_live.difference_update(int(ip) for ip in arr)
+        return self._acct_rows(out)
+
+    def acct_export(self):
+        """Every live entry, from a host-side view of the table blob."""
+        import numpy as np
+        if self.acct is None:
+            return np.zeros(0, dtype=abi.ACCT_ENTRY_DTYPE)
+        arr = self.acct.cpu().numpy().view(np.dtype(abi.ACCT_ENTRY_DTYPE))
+        return arr[(arr["key"] != 0) &
+                   (arr["key"] != 0xFFFFFFFFFFFFFFFF)].copy()
+
+    @property
+    def acct_count(self) -> int:
+        return len(self._acct_live)
+
+    def _acct_slots(self, n):
+        """The uplink's slot[] scratch, grown to the largest batch seen."""
+        if self._acct_slot is None or self._acct_slot.numel() < n:
+            self._acct_slot = self.torch.empty(
+                max(n, 8192), dtype=self.torch.int32, device=self.device)
+        return self._acct_slot
+
     # ================================================ batched processing
     def make_batch(self, frames: Sequence[bytes], stride: int = 512):
         """Pack frames into a device batch (data[n,stride], len[n])."""
@@ -516,12 +611,22 @@ class HipLauncher:
         With PPPoE sessions provisioned, pppoe_decap() runs first (so the
         classifier and the pipeline see IPoE frames and `lens` is updated
         in place), frames it rejects leave with DROP, and the per-packet
-        state stays reachable as last_pppoe_state."""
+        state stays reachable as last_pppoe_state.
+
+        With accounting entries live (acct_add), acct_resolve runs after
+        the decap and acct_commit last of all, on the final verdicts."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
         state = self.pppoe_decap(data, lens) \
             if self._pppoe_live and n else None
+        # accounting pre-pass: the subscriber's source address goes before
+        # SNAT overwrites it
+        slot = None
+        if self._acct_live and n:
+            slot = self._acct_slots(n)
+            self.ext.acct_resolve(data, lens, slot, self.acct)
+            self.acct_launches["resolve"] += 1
         if order is None and sort_by_type and n > 64:
             cls = self.torch.empty(n, dtype=self.torch.uint8,
                                    device=self.device)
@@ -539,12 +644,16 @@ class HipLauncher:
         if state is not None:
             verdict.masked_fill_(state == abi.PPPOE_REJECT, abi.DROP)
             self.last_pppoe_state = state
+        if slot is not None:
+            self.ext.acct_commit(self.acct, slot, verdict, out_len, now)
+            self.acct_launches["commit"] += 1
         return verdict, out_len
 
     def downlink(self, data, lens, now_ns: Optional[int] = None):
         """Fused NAT44 DNAT -> QoS-egress return path.  With PPPoE sessions
         provisioned, pppoe_encap() follows: `lens` is updated in place and
-        the state stays reachable as last_pppoe_state."""
+        the state stays reachable as last_pppoe_state.  With accounting
+        entries live, acct_downlink bills the frames in between."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
@@ -557,6 +666,10 @@ class HipLauncher:
             self.nat_log_hdr, self.qos_egress, self.qos_stats, now,
             now // 10**9, order=None, downlink=True,
             masked=self.masked_compute)
+        if self._acct_live and n:
+            # before the encap: both directions count the IPoE length
+            self.ext.acct_downlink(data, lens, verdict, self.acct, now)
+            self.acct_launches["downlink"] += 1
         if self._pppoe_live and n:
             self.last_pppoe_state = self.pppoe_encap(data, lens, verdict)
         return verdict
@@ -993,6 +1106,43 @@ class GoldenLauncher:
                                                           stride)
             states.append(st)
         return states
+
+    # per-subscriber accounting (same records as HipLauncher's; the model
+    # has no capacity, so acct_log2 is accepted and never reached)
+    def _acct_rows(self, ips, pop=False):
+        import numpy as np
+        ips = [int(ip) & 0xFFFFFFFF for ip in ips]
+        if len(set(ips)) != len(ips):
+            raise ValueError("an accounting batch must not repeat an address")
+        out = np.zeros(len(ips), dtype=abi.ACCT_ENTRY_DTYPE)
+        for i, ip in enumerate(ips):
+            e = self.dp.acct.pop(ip, None) if pop else self.dp.acct.get(ip)
+            if e is not None:
+                out[i] = (abi.acct_key(ip),) + tuple(
+                    getattr(e, f) for f in abi.ACCT_COUNTERS)
+        return out
+
+    def acct_add(self, ips, reset=False):
+        from .golden import AcctRec
+        ips = [int(ip) & 0xFFFFFFFF for ip in ips]
+        if len(set(ips)) != len(ips):
+            raise ValueError("an accounting batch must not repeat an address")
+        for ip in ips:
+            if reset or ip not in self.dp.acct:
+                self.dp.acct[ip] = AcctRec()
+
+    def acct_read(self, ips):
+        return self._acct_rows(ips)
+
+    def acct_remove(self, ips):
+        return self._acct_rows(ips, pop=True)
+
+    def acct_export(self):
+        return self._acct_rows(list(self.dp.acct))
+
+    @property
+    def acct_count(self):
+        return len(self.dp.acct)
 
     # processing (frames as list[bytearray]); mirrors HipLauncher outputs
     def process_dhcp(self, frames, now_sec=None):

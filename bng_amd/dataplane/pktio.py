@@ -398,12 +398,17 @@ class Pump:
                     passed.append(orig)
                     self.stats["passed"] += 1
                     continue
+                # accounting brackets the stage chain like the launcher's
+                # two uplink passes: keyed on the source before SNAT
+                # rewrites it, billed by the chain's verdict
+                akey = dp.acct_resolve(fr, "src") if dp.acct else None
                 vd = self.launcher.dp.antispoof(bytes(fr))
                 if vd == abi.FWD:
                     fb = bytearray(fr)
                     vd = self.launcher.dp.nat44_egress(fb)
                     if vd == abi.FWD:
                         vd = self.launcher.dp.qos(bytes(fb), "ingress")
+                dp.acct_commit(akey, "uplink", len(fr), vd, dp.now_ns)
                 if vd == abi.FWD:
                     out_frames.append(bytes(fb))
                     self.stats["fwd"] += 1
@@ -477,6 +482,11 @@ class Pump:
             vd = self.launcher.dp.nat44_ingress(fb)
             if vd == abi.FWD:
                 vd = self.launcher.dp.qos(bytes(fb), "egress")
+            dp = self.launcher.dp
+            if dp.acct:
+                # keyed on the DNAT-rewritten destination, before the encap
+                dp.acct_commit(dp.acct_resolve(fb, "dst"), "downlink",
+                               len(fb), vd, dp.now_ns)
             if self.launcher.dp.pppoe_sessions:
                 _pst, vd, _L = self.launcher.dp.pppoe_encap(
                     fb, vd, self.stride)

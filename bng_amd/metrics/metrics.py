@@ -183,6 +183,8 @@ class Metrics:
                 for name, v in launcher.pppoe_get_stats().items():
                     self.dataplane_stat.labels("pppoe", name).set(v)
                     self.pppoe_fastpath[name].set(v)
+            if getattr(launcher, "acct_count", 0):
+                self._collect_session_bytes(launcher.acct_export())
         if dhcp_server is not None:
             for pool_stats in dhcp_server.pools.all_stats():
                 pid = str(pool_stats["pool_id"])
@@ -193,6 +195,20 @@ class Metrics:
                         pool_stats["allocated"] / total)
         if session_manager is not None:
             self.sessions_active.labels("dhcp").set(session_manager.count())
+
+    def _collect_session_bytes(self, entries):
+        """bng_session_bytes_{in,out}_total from the live accounting
+        entries' sums.  The families are Counters, so each pull adds what
+        the sum grew by; a sum that shrank (subscribers left with their
+        counters) restarts the baseline and adds nothing."""
+        sums = (int(entries["up_bytes"].sum()),
+                int(entries["down_bytes"].sum()))
+        last = getattr(self, "_session_bytes_last", (0, 0))
+        for ctr, now, before in zip(
+                (self.session_bytes_in, self.session_bytes_out), sums, last):
+            if now > before:
+                ctr.labels("dhcp").inc(now - before)
+        self._session_bytes_last = sums
 
     # --------------------------------------------------------------- HTTP
     def serve(self, host: str = "127.0.0.1", port: int = 9090):

@@ -27,6 +27,8 @@ class SessionRecord:
     last_interim: float = 0.0
     stopped: bool = False
     terminate_cause: int = 0
+    input_packets: int = 0
+    output_packets: int = 0
 
 
 class AccountingManager:
@@ -44,14 +46,19 @@ class AccountingManager:
         self._stop = threading.Event()
         self._threads: List[threading.Thread] = []
         self._counter_fetcher = None
+        # packet attributes go out only once a fetcher supplies packet
+        # counts: without one the requests are what they always were
+        self._send_packets = False
         if persist_path:
             self._recover_orphans()
 
     def set_counter_fetcher(self, fn):
         """Live octet-counter pull before each interim/stop record (ref
         accounting.go SetCounterFetcher) — the dataplane integration
-        point: fn(session_record) -> (input_octets, output_octets) or
-        None to keep the pushed values."""
+        point: fn(session_record) -> (input_octets, output_octets), or
+        (input_octets, output_octets, input_packets, output_packets), or
+        None to keep the pushed values.  Records carry the packet
+        attributes from the first 4-tuple on."""
         self._counter_fetcher = fn
 
     def _refresh_counters(self, rec: "SessionRecord"):
@@ -62,7 +69,10 @@ class AccountingManager:
         except Exception:
             return
         if got:
-            rec.input_octets, rec.output_octets = got
+            rec.input_octets, rec.output_octets = got[0], got[1]
+            if len(got) >= 4:
+                rec.input_packets, rec.output_packets = got[2], got[3]
+                self._send_packets = True
 
     # ---------------------------------------------------------- lifecycle
     def start(self):
@@ -115,11 +125,14 @@ class AccountingManager:
     # ------------------------------------------------------------- sends
     def _try_send(self, status: int, rec: SessionRecord) -> bool:
         try:
+            pk = {"input_packets": rec.input_packets,
+                  "output_packets": rec.output_packets} \
+                if self._send_packets else {}
             return self.client.send_accounting(
                 status, rec.session_id, rec.username, rec.framed_ip,
                 rec.input_octets, rec.output_octets,
                 int(time.time() - rec.start_time), rec.terminate_cause,
-                rec.mac)
+                rec.mac, **pk)
         except Exception:
             return False
 
@@ -142,9 +155,24 @@ class AccountingManager:
                         rec.last_interim = now
                         due.append(rec)
             for rec in due:
-                self._refresh_counters(rec)
-                if not self._try_send(rp.ACCT_INTERIM, rec):
-                    self._queue(rp.ACCT_INTERIM, rec)
+                self._send_interim(rec)
+
+    def _send_interim(self, rec: SessionRecord):
+        self._refresh_counters(rec)
+        if not self._try_send(rp.ACCT_INTERIM, rec):
+            self._queue(rp.ACCT_INTERIM, rec)
+
+    def send_interim(self, session_id: str) -> bool:
+        """An Interim-Update for one session now, outside the schedule
+        (operator request, CoA); False when the session is unknown."""
+        with self._lock:
+            rec = self.sessions.get(session_id)
+            if rec is not None:
+                rec.last_interim = time.time()
+        if rec is None:
+            return False
+        self._send_interim(rec)
+        return True
 
     def _retry_loop(self):
         while not self._stop.wait(min(self.retry_interval, 0.5)):

@@ -200,8 +200,13 @@ class Client:
                         username: str = "", framed_ip: str = "",
                         input_octets: int = 0, output_octets: int = 0,
                         session_time: int = 0, terminate_cause: int = 0,
-                        mac: str = "") -> bool:
-        """Acct Start/Interim/Stop (ref client.go:250 SendAccounting)."""
+                        mac: str = "",
+                        input_packets: Optional[int] = None,
+                        output_packets: Optional[int] = None) -> bool:
+        """Acct Start/Interim/Stop (ref client.go:250 SendAccounting).
+        Octets beyond 32 bits carry their high word in Acct-*-Gigawords
+        (RFC 2869; ref client.go:297-303); the packet attributes go out
+        only when a count is given."""
         ident = self._next_ident()
         pkt = rp.Packet(rp.ACCOUNTING_REQUEST, ident)
         pkt.add(rp.ACCT_STATUS_TYPE, status_type)
@@ -218,7 +223,17 @@ class Client:
         if status_type in (rp.ACCT_INTERIM, rp.ACCT_STOP):
             pkt.add(rp.ACCT_INPUT_OCTETS, input_octets & 0xFFFFFFFF)
             pkt.add(rp.ACCT_OUTPUT_OCTETS, output_octets & 0xFFFFFFFF)
+            if input_packets is not None:
+                pkt.add(rp.ACCT_INPUT_PACKETS, input_packets & 0xFFFFFFFF)
+            if output_packets is not None:
+                pkt.add(rp.ACCT_OUTPUT_PACKETS, output_packets & 0xFFFFFFFF)
             pkt.add(rp.ACCT_SESSION_TIME, session_time)
+            if input_octets > 0xFFFFFFFF:
+                pkt.add(rp.ACCT_INPUT_GIGAWORDS,
+                        (input_octets >> 32) & 0xFFFFFFFF)
+            if output_octets > 0xFFFFFFFF:
+                pkt.add(rp.ACCT_OUTPUT_GIGAWORDS,
+                        (output_octets >> 32) & 0xFFFFFFFF)
         if status_type == rp.ACCT_STOP and terminate_cause:
             pkt.add(rp.ACCT_TERMINATE_CAUSE, terminate_cause)
         req_auth = rp.acct_request_authenticator(pkt, self.secret)

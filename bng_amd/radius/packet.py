@@ -52,6 +52,8 @@ ACCT_SESSION_TIME = 46
 ACCT_INPUT_PACKETS = 47
 ACCT_OUTPUT_PACKETS = 48
 ACCT_TERMINATE_CAUSE = 49
+ACCT_INPUT_GIGAWORDS = 52      # RFC 2869
+ACCT_OUTPUT_GIGAWORDS = 53
 CHAP_CHALLENGE = 60
 NAS_PORT_TYPE = 61
 ERROR_CAUSE = 101
