@@ -373,6 +373,9 @@ struct pktctx {
   int vlan_offset;
   uint16_t s_tag, c_tag;
   bool tagged;
+  /* ports or ICMP id parsed.  Never set for a non-first fragment (no L4
+   * header in the frame) or an ICMP message that is not a query (no id
+   * field): their L4 bytes are neither read nor written */
   bool l4_ok;
   /* register window: bswapped words of bytes 0..47 when the fast parse
    * ran (untagged ihl=5).  TA (vector-memory address) occupancy is the
@@ -427,6 +430,12 @@ BNG_DEV void rg_flush16_47(pktctx& c) {
                     __builtin_bswap32(c.W[11]));
 }
 
+/* ICMP types with an id at bytes 4..5: echo, timestamp, information and
+ * address-mask requests and replies (0, 8, 13..18) */
+BNG_DEV bool icmp_is_query(uint32_t type) {
+  return type <= 18 && ((0x7E101u >> type) & 1u);
+}
+
 /* Vectorized parse fast path: untagged IPv4 with ihl=5 (the 64B-mix hot
  * case).  Three dwordx4 loads replace ~30 dependent byte loads; fields
  * are extracted from registers with constant shifts.  Returns false to
@@ -456,7 +465,9 @@ BNG_DEV bool parse_pkt_fast(pktctx& c, uint8_t* p, int len) {
   c.saddr = (BNG_H(26) << 16) | BNG_H(28);
   c.daddr = (BNG_H(30) << 16) | BNG_H(32);
   c.l4_off = 34;
-  if (c.proto == 6 && len >= 54) {
+  if (BNG_H(20) & 0x1FFFu) {
+    /* non-first fragment: no L4 header */
+  } else if (c.proto == 6 && len >= 54) {
     c.sport = (uint16_t)BNG_H(34);
     c.dport = (uint16_t)BNG_H(36);
     c.tcp_flags = (uint8_t)BNG_B(47);
@@ -466,8 +477,10 @@ BNG_DEV bool parse_pkt_fast(pktctx& c, uint8_t* p, int len) {
     c.dport = (uint16_t)BNG_H(36);
     c.l4_ok = true;
   } else if (c.proto == 1 && len >= 42) {
-    c.icmp_id = (uint16_t)BNG_H(38);
-    c.l4_ok = true;
+    if (icmp_is_query(BNG_B(34))) {
+      c.icmp_id = (uint16_t)BNG_H(38);
+      c.l4_ok = true;
+    }
   }
   #undef BNG_B
   #undef BNG_H
@@ -498,13 +511,19 @@ BNG_DEV bool parse_pkt_slow(pktctx& c, uint8_t* p, int len, bool want_vlan) {
     }
   }
   if (proto != 0x0800 || len < off + 20) return false;
+  /* not version 4, or a header shorter than the fixed 20 bytes: not an
+   * IPv4 packet, whatever the ethertype says */
+  uint8_t vihl = p[off];
+  if ((vihl >> 4) != 4 || (vihl & 0xF) < 5) return false;
   c.ip_off = off;
   c.proto = p[off + 9];
   c.saddr = ld_u32be(p + off + 12);
   c.daddr = ld_u32be(p + off + 16);
-  int ihl = (p[off] & 0xF) * 4;
+  int ihl = (vihl & 0xF) * 4;
   c.l4_off = off + ihl;
-  if (c.proto == 6 && len >= c.l4_off + 20) {
+  if (ld_u16be(p + off + 6) & 0x1FFF) {
+    /* non-first fragment: no L4 header */
+  } else if (c.proto == 6 && len >= c.l4_off + 20) {
     c.sport = ld_u16be(p + c.l4_off);
     c.dport = ld_u16be(p + c.l4_off + 2);
     c.tcp_flags = p[c.l4_off + 13];
@@ -514,8 +533,10 @@ BNG_DEV bool parse_pkt_slow(pktctx& c, uint8_t* p, int len, bool want_vlan) {
     c.dport = ld_u16be(p + c.l4_off + 2);
     c.l4_ok = true;
   } else if (c.proto == 1 && len >= c.l4_off + 8) {
-    c.icmp_id = ld_u16be(p + c.l4_off + 4);
-    c.l4_ok = true;
+    if (icmp_is_query(p[c.l4_off])) {
+      c.icmp_id = ld_u16be(p + c.l4_off + 4);
+      c.l4_ok = true;
+    }
   }
   return true;
 }
@@ -1190,6 +1211,20 @@ BNG_DEV uint16_t csum_upd16(uint16_t csum, uint16_t oldv, uint16_t newv) {
   return (uint16_t)~s;
 }
 
+/* TCP/UDP/ICMP from a NATed subscriber that parsed without l4_ok (the rare
+ * case, so the parser carries no flag for it and this looks again).  A
+ * non-first fragment or a non-query ICMP message has nothing to key a
+ * session on: the host slow path can reassemble and inspect, this one
+ * cannot.  What is left ends inside its L4 header and is forwarded. */
+BNG_DEV int nat_egress_no_l4(const pktctx& c, nat_flags& F) {
+  const uint8_t* p = c.p;
+  bool frag = (ld_u16be(p + c.ip_off + 6) & 0x1FFF) != 0;
+  bool not_query = c.proto == 1 && c.len >= c.l4_off + 8 &&
+                   !icmp_is_query(p[c.l4_off]);
+  if (frag || not_query) { F.passed = true; return BNG_PASS; }
+  return BNG_FWD;
+}
+
 /* SNAT (ref nat44_egress nat44.c:565-802); blk_pre/blk_pre_valid let the
  * fused pipeline supply an already-probed port block */
 BNG_DEV int nat_egress_process(pktctx& c, const nat_tables& T, nat_flags& F,
@@ -1205,7 +1240,7 @@ BNG_DEV int nat_egress_process(pktctx& c, const nat_tables& T, nat_flags& F,
 
   uint16_t sport, dport;
   if (c.proto == 6) {
-    if (!c.l4_ok) return BNG_FWD;
+    if (!c.l4_ok) return nat_egress_no_l4(c, F);
     sport = c.sport; dport = c.dport;
     if (cfg->flags & (BNG_NAT_FLAG_ALG_FTP | BNG_NAT_FLAG_ALG_SIP)) {
       if (nat_is_alg(cfg, dport, 6)) {
@@ -1216,7 +1251,7 @@ BNG_DEV int nat_egress_process(pktctx& c, const nat_tables& T, nat_flags& F,
       }
     }
   } else if (c.proto == 17) {
-    if (!c.l4_ok) return BNG_FWD;
+    if (!c.l4_ok) return nat_egress_no_l4(c, F);
     sport = c.sport; dport = c.dport;
     if (cfg->flags & BNG_NAT_FLAG_ALG_SIP) {
       if (nat_is_alg(cfg, dport, 17)) {
@@ -1227,7 +1262,7 @@ BNG_DEV int nat_egress_process(pktctx& c, const nat_tables& T, nat_flags& F,
       }
     }
   } else if (c.proto == 1) {
-    if (!c.l4_ok) return BNG_FWD;
+    if (!c.l4_ok) return nat_egress_no_l4(c, F);
     sport = c.icmp_id; dport = 0;
   } else {
     return BNG_FWD;

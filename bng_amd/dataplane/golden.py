@@ -133,6 +133,11 @@ class AcctRec:
     last_seen: int = 0
 
 
+# ICMP types that carry an id at bytes 4..5: echo, timestamp, information
+# and address-mask, request and reply.  Every other type is an error or a
+# redirect, whose bytes 4..7 mean something else.
+ICMP_QUERY_TYPES = frozenset((0, 8, 13, 14, 15, 16, 17, 18))
+
 DEFAULT_PRIVATE_RANGES = [
     # is_private_ip inline ranges, ref nat44.c:340-363
     (0x0A000000, 0xFF000000),                    # 10.0.0.0/8
@@ -224,8 +229,12 @@ class GoldenDataplane:
         if proto != ETH_P_IP or n < off + 20:
             return PASS, n
         ip_off = off
+        if not self._ipv4_header_ok(frame, ip_off):
+            return PASS, n
         if frame[ip_off + 9] != 17:      # UDP
             return PASS, n
+        if struct.unpack_from(">H", frame, ip_off + 6)[0] & 0x1FFF:
+            return PASS, n               # non-first fragment: no UDP header
         ihl = (frame[ip_off] & 0xF) * 4
         udp_off = ip_off + ihl
         if n < udp_off + 8:
@@ -431,38 +440,65 @@ class GoldenDataplane:
             return port
         return 0
 
+    @staticmethod
+    def _ipv4_header_ok(frame, ip_off: int) -> bool:
+        """Version 4 and ihl >= 5 (parse_pkt_slow).  The reference takes
+        any header under ethertype 0x0800 (nat44.c:606); we do not: with
+        ihl < 5 the "L4 header" lies inside the IP header and SNAT would
+        write a port over it."""
+        return frame[ip_off] >> 4 == 4 and (frame[ip_off] & 0xF) >= 5
+
     def _parse_l3l4(self, frame) -> Optional[dict]:
+        """None: not IPv4.  `short`: the frame ends inside the TCP/UDP/ICMP
+        header; the NAT stages forward it, but a private source without a
+        NAT context is passed to the host first, as in the kernel.  `no_l4` is a TCP/UDP/ICMP packet without a flow identifier the fast
+        path may use — a non-first fragment, whose L4 bytes are payload, or
+        an ICMP message that is not a query and so has no id.  The reference
+        reads ports and ids from both (nat44.c:606-648); we read and write
+        none of their L4 bytes."""
         n = len(frame)
         if n < 34 or struct.unpack_from(">H", frame, 12)[0] != ETH_P_IP:
             return None
         ip_off = 14
+        if not self._ipv4_header_ok(frame, ip_off):
+            return None
         ihl = (frame[ip_off] & 0xF) * 4
         proto = frame[ip_off + 9]
         saddr, daddr = struct.unpack_from(">II", frame, ip_off + 12)
         l4 = ip_off + ihl
-        r = dict(ip_off=ip_off, l4=l4, proto=proto, saddr=saddr, daddr=daddr)
-        if proto == 6 and n >= l4 + 20:
+        r = dict(ip_off=ip_off, l4=l4, proto=proto, saddr=saddr, daddr=daddr,
+                 no_l4=False, short=False)
+        if struct.unpack_from(">H", frame, ip_off + 6)[0] & 0x1FFF:
+            r["no_l4"] = proto in (6, 17, 1)
+        elif proto == 6 and n >= l4 + 20:
             r["sport"], r["dport"] = struct.unpack_from(">HH", frame, l4)
             r["tcp_flags"] = frame[l4 + 13]
         elif proto == 17 and n >= l4 + 8:
             r["sport"], r["dport"] = struct.unpack_from(">HH", frame, l4)
         elif proto == 1 and n >= l4 + 8:
-            r["icmp_id"] = struct.unpack_from(">H", frame, l4 + 4)[0]
-        else:
-            return r if proto not in (6, 17, 1) else None
+            if frame[l4] in ICMP_QUERY_TYPES:
+                r["icmp_id"] = struct.unpack_from(">H", frame, l4 + 4)[0]
+            else:
+                r["no_l4"] = True
+        elif proto in (6, 17, 1):
+            r["short"] = True            # the frame ends inside the L4 header
         return r
 
     def nat44_egress(self, frame: bytearray) -> int:
-        """SNAT (ref nat44_egress nat44.c:565-802).  Returns verdict."""
+        """SNAT (ref nat44_egress nat44.c:565-802).  Returns verdict.
+        Unlike the reference, a non-first fragment or a non-query ICMP
+        message from a NATed subscriber goes to the host (PASS), untouched."""
         h = self._parse_l3l4(frame)
         if h is None:
             return FWD
         if not self._is_private(h["saddr"]):
             return FWD
         blk = self.subnat.get(h["saddr"])
-        if blk is None:
+        if blk is None or h["no_l4"]:
             self.nat_stats[abi.NS_PASSED] += 1
             return PASS
+        if h["short"]:
+            return FWD
         proto = h["proto"]
         if proto == 6:
             sport, dport = h["sport"], h["dport"]
@@ -579,9 +615,10 @@ class GoldenDataplane:
         return FWD
 
     def nat44_ingress(self, frame: bytearray) -> int:
-        """DNAT (ref nat44_ingress nat44.c:805-948)."""
+        """DNAT (ref nat44_ingress nat44.c:805-948).  Unlike the reference,
+        non-first fragments and non-query ICMP are forwarded unread."""
         h = self._parse_l3l4(frame)
-        if h is None:
+        if h is None or h["no_l4"] or h["short"]:
             return FWD
         proto = h["proto"]
         if proto == 6 or proto == 17:
@@ -670,8 +707,10 @@ class GoldenDataplane:
         """direction 'egress' keys dst IP (download), 'ingress' src IP."""
         if len(frame) < 34 or struct.unpack_from(">H", frame, 12)[0] != ETH_P_IP:
             return FWD
+        if not self._ipv4_header_ok(frame, 14):
+            return FWD
         saddr, daddr = struct.unpack_from(">II", frame, 14 + 12)
-        table = self.qos_egress if direction == "egress" else self.qos_ingress
+        table =self.qos_egress if direction == "egress" else self.qos_ingress
         tb = table.get(daddr if direction == "egress" else saddr)
         if tb is None:
             return FWD
