@@ -434,6 +434,10 @@ class BNG:
             portal_ip=p_ip,
             portal_port=int(p_port) if p_port else 8080).start()
         self._defer(self.walledgarden.stop)
+        # the garden's decisions are enforced on the dataplane: the gate
+        # around the uplink and downlink pipelines (GPU or golden model)
+        from ..walledgarden.dataplane import attach_dataplane
+        attach_dataplane(self.walledgarden, self.launcher)
 
         # 4. pools + DHCP server (main.go:567-594, :1244)
         from ..dhcp.pool import PoolConfig, PoolManager
@@ -917,6 +921,8 @@ class BNG:
                 return self.pppoe.handle_frame(frame) or None
             if et == 0x0806:
                 return self._arp_reply(frame)
+            if et == 0x0800 and self._garden_redirect(frame):
+                return None
         try:
             p = parse_dhcp_frame(frame)
         except (AssertionError, IndexError, ValueError):
@@ -928,6 +934,27 @@ class BNG:
             return None
         resp = self.dhcp_server.handle(msg)
         return resp.encode() if resp else None
+
+    def _garden_redirect(self, frame: bytes) -> bool:
+        """A TCP frame the walled-garden gate passed to the host (gate
+        REDIRECT): classify() counts the redirect and fires the on_redirect
+        callbacks.  True when the frame was a quarantined subscriber's TCP;
+        nothing is answered — the DNS intercept steers the browser to the
+        portal, which is on the allow-list."""
+        from ..dataplane.packets import u32_to_ip
+        wg = getattr(self, "walledgarden", None)
+        if wg is None or len(frame) < 34 or frame[14] >> 4 != 4 or \
+                frame[23] != 6:
+            return False
+        mac = ":".join(f"{b:02x}" for b in frame[6:12])
+        if not wg.is_quarantined(mac):
+            return False
+        l4 = 14 + 4 * (frame[14] & 0xF)
+        if l4 < 34 or len(frame) < l4 + 4:
+            return False
+        wg.classify(mac, u32_to_ip(int.from_bytes(frame[30:34], "big")),
+                    int.from_bytes(frame[l4 + 2:l4 + 4], "big"), 6)
+        return True
 
     def _arp_reply(self, frame: bytes):
         """Answer who-has for our server IP (the reference leans on
@@ -1031,6 +1058,8 @@ class BNG:
             out["nat"] = self.nat.get_stats()
         if getattr(self, "walledgarden", None):
             out["walledgarden"] = self.walledgarden.get_stats()
+        if hasattr(self.launcher, "wg_get_stats"):
+            out["walledgarden_gate"] = self.launcher.wg_get_stats()
         if getattr(self, "resilience", None):
             out["resilience"] = {
                 "state": self.resilience.state,

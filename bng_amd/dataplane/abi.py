@@ -18,6 +18,9 @@ MAX_SUBNAT_LOG2 = 21
 MAX_QOS_LOG2 = 21
 MAX_BINDINGS_LOG2 = 21
 MAX_ACCT_LOG2 = 21
+MAX_WG_LOG2 = 21
+MAX_WG_ALLOWED = 64
+MAX_WG_REDIRECT_PORTS = 8
 MAX_PROBE = 128
 MAX_PRIVATE_RANGES = 64
 MAX_ALLOWED_RANGES = 256
@@ -320,6 +323,70 @@ def acct_key(ip: int) -> int:
     return (1 << 32) | (ip & 0xFFFFFFFF)
 
 
+# walled-garden gate: entry states, per-packet gate codes, counters
+WG_WALLED, WG_BLOCKED = 1, 2
+WG_MAC_MASK = (1 << 48) - 1
+WG_STATE_SHIFT = 56
+WG_NONE, WG_ALLOW, WG_REDIRECT, WG_DROP_WALLED, WG_DROP_BLOCKED, \
+    WG_DROP_MAC = range(6)
+WS_UP_ALLOWED, WS_UP_REDIRECTED, WS_UP_DROP_WALLED, WS_UP_DROP_BLOCKED, \
+    WS_UP_DROP_MAC, WS_DOWN_ALLOWED, WS_DOWN_DROP_WALLED, \
+    WS_DOWN_DROP_BLOCKED = range(8)
+WG_NSTATS = 8
+WG_STAT_NAMES = ["up_allowed", "up_redirected", "up_drop_walled",
+                 "up_drop_blocked", "up_drop_mac", "down_allowed",
+                 "down_drop_walled", "down_drop_blocked"]
+WG_DEFAULT_REDIRECT_PORTS = (80, 8080)
+
+
+class WgEntry(C.Structure):
+    """Quarantine state of one subscriber address, keyed by wg_key(ip)."""
+    _fields_ = [("key", C.c_uint64), ("mac_state", C.c_uint64)]
+
+
+class WgConfig(C.Structure):
+    """What a quarantined subscriber may reach (sorted, binary-searched)."""
+    _fields_ = [("n_allowed", C.c_uint32), ("n_allowed_ips", C.c_uint32),
+                ("n_redirect_ports", C.c_uint32), ("_pad", C.c_uint32),
+                ("allowed_key", C.c_uint64 * MAX_WG_ALLOWED),
+                ("allowed_ip", C.c_uint32 * MAX_WG_ALLOWED),
+                ("redirect_port", C.c_uint16 * MAX_WG_REDIRECT_PORTS)]
+
+
+# bng_wg_entry as a numpy record (wg_set / wg_export)
+WG_ENTRY_DTYPE = [("key", "<u8"), ("mac_state", "<u8")]
+
+
+def wg_key(ip: int) -> int:
+    """Garden table key; bit 32 keeps it clear of EMPTY and TOMBSTONE for
+    any address."""
+    return (1 << 32) | (ip & 0xFFFFFFFF)
+
+
+def wg_mac_state(mac: int, state: int) -> int:
+    return (mac & WG_MAC_MASK) | ((state & 0xFF) << WG_STATE_SHIFT)
+
+
+def wg_allowed_key(ip: int, port: int, proto: int) -> int:
+    return ((ip & 0xFFFFFFFF) << 32) | ((port & 0xFFFF) << 16) | (proto & 0xFF)
+
+
+def wg_fold_config(allowed, redirect_ports=WG_DEFAULT_REDIRECT_PORTS):
+    """(sorted unique allowed keys, sorted distinct addresses, redirect
+    ports) of a garden config; ValueError beyond the ABI's capacity."""
+    keys = sorted({wg_allowed_key(int(ip), int(port), int(proto))
+                   for ip, port, proto in allowed})
+    ports = sorted({int(p) & 0xFFFF for p in redirect_ports})
+    if len(keys) > MAX_WG_ALLOWED:
+        raise ValueError(f"walled garden: {len(keys)} allowed destinations, "
+                         f"at most {MAX_WG_ALLOWED}")
+    if len(ports) > MAX_WG_REDIRECT_PORTS:
+        raise ValueError(f"walled garden: {len(ports)} redirect ports, "
+                         f"at most {MAX_WG_REDIRECT_PORTS}")
+    ips = sorted({k >> 32 for k in keys})
+    return keys, ips, ports
+
+
 EXPECTED_SIZES = {
     "bng_sub_entry": (SubEntry, 32),
     "bng_ip_pool": (IpPool, 28),
@@ -341,6 +408,8 @@ EXPECTED_SIZES = {
     "bng_pppoe_sess": (PppoeSess, 16),
     "bng_pppoe_ip": (PppoeIp, 16),
     "bng_acct_entry": (AcctEntry, 64),
+    "bng_wg_entry": (WgEntry, 16),
+    "bng_wg_config": (WgConfig, 16 + 64 * 8 + 64 * 4 + 8 * 2),
 }
 
 

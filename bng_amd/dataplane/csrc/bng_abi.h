@@ -39,6 +39,9 @@ enum {
   BNG_MAX_QOS_LOG2         = 21,
   BNG_MAX_BINDINGS_LOG2    = 21,
   BNG_MAX_ACCT_LOG2        = 21, /* 2M slots for 1M accounted subscribers  */
+  BNG_MAX_WG_LOG2          = 21, /* 2M slots for 1M quarantined subscribers */
+  BNG_MAX_WG_ALLOWED       = 64, /* walled-garden (ip, port, proto) keys    */
+  BNG_MAX_WG_REDIRECT_PORTS = 8,
   BNG_MAX_PROBE            = 128, /* linear-probe bound before declaring full */
   BNG_MAX_PRIVATE_RANGES   = 64,  /* bpf/nat44.c:314-320 nat_private_ranges */
   BNG_MAX_ALLOWED_RANGES   = 256, /* bpf/antispoof.c:113-119 allowed_ranges_v4 */
@@ -395,6 +398,62 @@ typedef struct bng_acct_entry {
   uint64_t down_drop_pkts;
   uint64_t last_seen;      /* batch now_ns of the last FORWARDED packet         */
 } bng_acct_entry;  /* 64 B */
+
+/* ------------------------------------------------- walled-garden gate */
+/* Quarantine state of one subscriber address, consulted for every untagged
+ * IPv4 data frame in both directions by the gate kernels around the fused
+ * pipelines.  No reference analog: the reference keeps the walled-garden
+ * state machine in user space (pkg/walledgarden/manager.go) and has no
+ * walled_garden.c.  Keyed by the subscriber IPv4 like the accounting table;
+ * one 16-B load serves a probe step.  Open addressing with the usual
+ * EMPTY / TOMBSTONE keys and BNG_MAX_PROBE bound; host-inserted
+ * (stream-ordered), read-only for the packet kernels. */
+#define BNG_WG_KEY(ip) ((1ULL << 32) | (uint64_t)(uint32_t)(ip))  /* never 0 / ~0 */
+#define BNG_WG_MAC_MASK    0x0000FFFFFFFFFFFFULL
+#define BNG_WG_STATE_SHIFT 56
+
+enum bng_wg_state {
+  BNG_WG_WALLED  = 1,  /* quarantined: allow-list, portal redirect, else drop */
+  BNG_WG_BLOCKED = 2,  /* no service at all                                  */
+};
+
+typedef struct bng_wg_entry {
+  uint64_t key;        /* BNG_WG_KEY(ip); 0 empty, ~0 tombstone             */
+  uint64_t mac_state;  /* bits 47:0 subscriber MAC (as mac_to_u64),
+                          bits 63:56 bng_wg_state                           */
+} bng_wg_entry;  /* 16 B */
+
+/* What a quarantined subscriber may reach.  allowed_key is sorted and
+ * unique, allowed_ip holds the sorted distinct addresses of those keys
+ * (the any-port rule for frames without readable ports); both are
+ * binary-searched. */
+typedef struct bng_wg_config {
+  uint32_t n_allowed;
+  uint32_t n_allowed_ips;
+  uint32_t n_redirect_ports;
+  uint32_t _pad;
+  uint64_t allowed_key[BNG_MAX_WG_ALLOWED];  /* ip<<32 | port<<16 | proto,
+                                                host order                  */
+  uint32_t allowed_ip[BNG_MAX_WG_ALLOWED];
+  uint16_t redirect_port[BNG_MAX_WG_REDIRECT_PORTS];  /* TCP, to the host   */
+} bng_wg_config;  /* 800 B */
+
+/* per-packet gate code written by the gate kernels */
+enum bng_wg_gate {
+  BNG_WG_NONE = 0,      /* not in the garden: the pipeline's verdict stands */
+  BNG_WG_ALLOW,         /* allow-listed: FWD, bytes untouched, no NAT       */
+  BNG_WG_REDIRECT,      /* uplink HTTP: PASS, the host redirects            */
+  BNG_WG_DROP_WALLED,
+  BNG_WG_DROP_BLOCKED,
+  BNG_WG_DROP_MAC,      /* uplink: source MAC is not the quarantined one    */
+};
+
+enum bng_wg_stat {
+  BNG_WS_UP_ALLOWED = 0, BNG_WS_UP_REDIRECTED, BNG_WS_UP_DROP_WALLED,
+  BNG_WS_UP_DROP_BLOCKED, BNG_WS_UP_DROP_MAC,
+  BNG_WS_DOWN_ALLOWED, BNG_WS_DOWN_DROP_WALLED, BNG_WS_DOWN_DROP_BLOCKED,
+  BNG_WG_NSTATS
+};
 
 /* ----------------------------------------------------------- ring header */
 /* Device->host ordered log ring: device atomically bumps widx; host reads

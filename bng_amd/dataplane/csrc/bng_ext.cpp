@@ -570,6 +570,99 @@ void acct_delete(torch::Tensor table, torch::Tensor ips, torch::Tensor out) {
                          out.data_ptr(), cur_stream());
 }
 
+/* Walled-garden gate.  The packet kernels read rows with 16-B loads and
+ * index verdict / out_len / gate / order by packet id or position, so every
+ * size is checked here. */
+uint32_t wg_table_mask(const torch::Tensor& table) {
+  return dev_table_mask(table, sizeof(bng_wg_entry), "wg");
+}
+
+void check_wg_common(const torch::Tensor& data, const torch::Tensor& in_len,
+                     const torch::Tensor& verdict, const torch::Tensor& gate,
+                     const torch::Tensor& cfg, const torch::Tensor& stats) {
+  check_dev(data, "data"); check_dev(in_len, "in_len");
+  TORCH_CHECK(data.dim() == 2 && data.element_size() == 1,
+              "data must be [n, stride] bytes");
+  TORCH_CHECK(data.size(0) == in_len.numel() && in_len.element_size() == 2 &&
+              in_len.numel() <= INT_MAX,
+              "in_len must hold one 16-bit length per row");
+  TORCH_CHECK(data.size(1) >= 64 && data.size(1) % 16 == 0 &&
+              data.size(1) <= 65535,
+              "the walled-garden gate needs a stride that is a multiple of "
+              "16, 64..65535");
+  TORCH_CHECK(((uintptr_t)data.data_ptr() & 15) == 0,
+              "the walled-garden gate needs a 16-byte aligned batch");
+  check_dev(verdict, "verdict"); check_dev(gate, "gate");
+  check_dev(cfg, "wg_cfg"); check_dev(stats, "stats");
+  TORCH_CHECK(verdict.numel() == in_len.numel() &&
+              verdict.element_size() == 1 &&
+              gate.numel() == in_len.numel() && gate.element_size() == 1,
+              "verdict and gate must hold one byte per row");
+  TORCH_CHECK(nbytes(cfg) >= sizeof(bng_wg_config) &&
+              ((uintptr_t)cfg.data_ptr() & 7) == 0, "wg_cfg too small");
+  TORCH_CHECK(nbytes(stats) >= BNG_WG_NSTATS * sizeof(uint64_t),
+              "stats too small");
+}
+
+void wg_uplink(torch::Tensor data, torch::Tensor in_len,
+               torch::Tensor verdict, torch::Tensor out_len,
+               torch::Tensor gate, c10::optional<torch::Tensor> order_in,
+               torch::Tensor order_out, torch::Tensor table,
+               torch::Tensor cfg, torch::Tensor stats) {
+  check_wg_common(data, in_len, verdict, gate, cfg, stats);
+  check_dev(out_len, "out_len"); check_dev(order_out, "order_out");
+  int64_t n = in_len.numel();
+  TORCH_CHECK(out_len.element_size() == 2 && out_len.numel() == n,
+              "out_len must hold one 16-bit length per row");
+  TORCH_CHECK(order_out.element_size() == 4 && order_out.numel() >= n,
+              "order_out must hold one int32 per row");
+  if (order_in.has_value()) {
+    check_dev(*order_in, "order");
+    TORCH_CHECK(order_in->element_size() == 4 && order_in->numel() >= n,
+                "order must hold one int32 per row");
+  }
+  uint32_t mask = wg_table_mask(table);
+  if (n == 0) return;
+  bng_launch_wg_uplink(
+      data.data_ptr(), in_len.data_ptr(), verdict.data_ptr(),
+      out_len.data_ptr(), gate.data_ptr(),
+      order_in.has_value() ? order_in->data_ptr() : nullptr,
+      order_out.data_ptr(), (int)n, (int)data.size(1), table.data_ptr(),
+      mask, cfg.data_ptr(), stats.data_ptr(), cur_stream());
+}
+
+void wg_downlink(torch::Tensor data, torch::Tensor in_len,
+                 torch::Tensor verdict, torch::Tensor gate,
+                 torch::Tensor table, torch::Tensor cfg,
+                 torch::Tensor stats) {
+  check_wg_common(data, in_len, verdict, gate, cfg, stats);
+  uint32_t mask = wg_table_mask(table);
+  int n = (int)in_len.numel();
+  if (n == 0) return;
+  bng_launch_wg_downlink(data.data_ptr(), in_len.data_ptr(),
+                         verdict.data_ptr(), gate.data_ptr(), n,
+                         (int)data.size(1), table.data_ptr(), mask,
+                         cfg.data_ptr(), stats.data_ptr(), cur_stream());
+}
+
+void wg_upsert(torch::Tensor table, torch::Tensor batch, torch::Tensor rc) {
+  uint32_t mask = wg_table_mask(table);
+  int n = upsert_count(batch, sizeof(bng_wg_entry), rc);
+  if (n == 0) return;
+  TORCH_CHECK(((uintptr_t)batch.data_ptr() & 7) == 0,
+              "batch must be 8-byte aligned");
+  bng_launch_wg_upsert(table.data_ptr(), mask, batch.data_ptr(), n,
+                       rc.data_ptr(), cur_stream());
+}
+
+void wg_delete(torch::Tensor table, torch::Tensor ips) {
+  uint32_t mask = wg_table_mask(table);
+  int n = acct_ip_count(ips);
+  if (n == 0) return;
+  bng_launch_wg_delete(table.data_ptr(), mask, ips.data_ptr(), n,
+                       cur_stream());
+}
+
 /* Fine-grained-coherent pinned host memory for the persistent-service
  * doorbell/rings.  torch's pin_memory allocates COARSE-grained host
  * memory on ROCm: a running kernel caches it and never observes host
@@ -662,6 +755,7 @@ py::dict layout_report() {
   SZ(bng_antispoof_config); SZ(bng_spoof_event); SZ(bng_ring_header);
   SZ(bng_svc_ctrl); SZ(bng_sess_export);
   SZ(bng_pppoe_sess); SZ(bng_pppoe_ip); SZ(bng_acct_entry);
+  SZ(bng_wg_entry); SZ(bng_wg_config);
 #undef SZ
   py::dict off;
   off["sub_entry.lease_expiry"] = offsetof(bng_sub_entry, lease_expiry);
@@ -688,6 +782,10 @@ py::dict layout_report() {
   off["acct_entry.down_bytes"] = offsetof(bng_acct_entry, down_bytes);
   off["acct_entry.up_drop_pkts"] = offsetof(bng_acct_entry, up_drop_pkts);
   off["acct_entry.last_seen"] = offsetof(bng_acct_entry, last_seen);
+  off["wg_entry.mac_state"] = offsetof(bng_wg_entry, mac_state);
+  off["wg_config.allowed_key"] = offsetof(bng_wg_config, allowed_key);
+  off["wg_config.allowed_ip"] = offsetof(bng_wg_config, allowed_ip);
+  off["wg_config.redirect_port"] = offsetof(bng_wg_config, redirect_port);
   d["offsets"] = off;
   return d;
 }
@@ -757,6 +855,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("acct_upsert", &acct_upsert);
   m.def("acct_read", &acct_read);
   m.def("acct_delete", &acct_delete);
+  m.def("wg_uplink", &wg_uplink, py::arg("data"), py::arg("in_len"),
+        py::arg("verdict"), py::arg("out_len"), py::arg("gate"),
+        py::arg("order_in"), py::arg("order_out"), py::arg("table"),
+        py::arg("cfg"), py::arg("stats"));
+  m.def("wg_downlink", &wg_downlink);
+  m.def("wg_upsert", &wg_upsert);
+  m.def("wg_delete", &wg_delete);
   m.def("set_acct_combine", &set_acct_combine, py::arg("rounds"));
   m.def("get_acct_combine", &get_acct_combine);
   m.def("nat_sweep", &nat_sweep);

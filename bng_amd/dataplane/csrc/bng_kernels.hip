@@ -2960,6 +2960,269 @@ __global__ void acct_delete_kernel(bng_acct_entry* t, uint32_t mask,
   if (e) rlx_store64(&e->key, BNG_KEY_TOMBSTONE);
 }
 
+/* ================================================== walled-garden gate */
+/* A quarantined subscriber has no port block and no QoS policy, so the
+ * fused uplink kernel would hand every data frame of theirs to the host,
+ * and a blocked subscriber who still holds a port block would keep full
+ * service.  The gate decides both on the device, for every untagged IPv4
+ * frame, in two small kernels around the pipelines (the uplink kernel has
+ * no registers to spare): wg_uplink_kernel ahead of the uplink pipeline,
+ * keyed on the source address, takes the frames it decides out of the
+ * pipeline's dispatch order; wg_downlink_kernel behind the downlink
+ * pipeline, keyed on the DNAT-rewritten destination, turns FWD into DROP.
+ * Neither is launched while no garden entry is live.  The decision table
+ * is GoldenDataplane.garden_uplink / garden_downlink.
+ *
+ * Rows are 16-B aligned (the extension checks), so the frame is read with
+ * the 16-B window loads of the PPPoE and accounting kernels: the three
+ * windows of bytes 0..47, and for a header with IP options the one (or
+ * two) that hold the ports.  No packet byte is written. */
+
+/* What the gate needs of a frame.  `eligible`: untagged IPv4, version 4,
+ * ihl >= 5, at least 34 B.  `ports`: TCP or UDP, first fragment, and the
+ * frame holds the whole TCP (20 B) / UDP (8 B) header; every other frame
+ * is portless. */
+struct wg_frame {
+  bool eligible, ports;
+  uint32_t saddr, daddr;      /* host ints of the BE fields */
+  uint32_t sport, dport;
+  uint32_t proto;
+  uint64_t smac;              /* as mac_to_u64 */
+};
+
+BNG_DEV wg_frame wg_parse(const uint8_t* p, int len, int stride) {
+  wg_frame f{false, false, 0, 0, 0, 0, 0, 0};
+  if (len > stride) len = stride;                    /* a row holds no more */
+  if (len < 34) return f;
+  uint4 h0 = *(const uint4*)p;                       /* bytes 0..15  */
+  if ((h0.w & 0xFFFFu) != 0x0008u) return f;         /* 08 00 */
+  uint32_t vihl = (h0.w >> 16) & 0xFFu;              /* byte 14 */
+  uint32_t ihl = vihl & 0xFu;
+  if ((vihl >> 4) != 4u || ihl < 5u) return f;
+  uint4 h1 = *(const uint4*)(p + 16);                /* bytes 16..31 */
+  uint4 h2 = row_ld16(p, 32, stride);                /* bytes 32..47 */
+  f.eligible = true;
+  f.smac = ((uint64_t)(__builtin_bswap32(h0.y) & 0xFFFFu) << 32) |
+           __builtin_bswap32(h0.z);                  /* bytes 6..11 */
+  f.proto = h1.y >> 24;                              /* byte 23 */
+  f.saddr = __builtin_bswap32((h1.z >> 16) | (h1.w << 16));   /* 26..29 */
+  f.daddr = __builtin_bswap32((h1.w >> 16) | (h2.x << 16));   /* 30..33 */
+  bool frag = (bswap16(h1.y & 0xFFFFu) & 0x1FFFu) != 0;       /* 20..21 */
+  int l4 = 14 + 4 * (int)ihl;                        /* 34..74 */
+  int need = f.proto == 6 ? 20 : 8;
+  if ((f.proto != 6 && f.proto != 17) || frag || l4 + need > len) return f;
+  /* sport and dport, bytes l4..l4+3.  They are inside the frame, so the
+   * 16-B window(s) that hold them are inside the row.  l4 is 2 mod 4: the
+   * four bytes straddle two dwords, and two windows when l4 is 14 mod 16.
+   * The dword pick is a select chain: indexing the window would put it in
+   * scratch memory. */
+  int w = l4 & ~15, k = (l4 & 15) >> 2;
+  uint4 a = w == 32 ? h2 : row_ld16(p, w, stride);
+  uint32_t lo = k == 0 ? a.x : k == 1 ? a.y : k == 2 ? a.z : a.w;
+  uint32_t hi;
+  if (k == 3) hi = row_ld16(p, w + 16, stride).x;
+  else hi = k == 0 ? a.y : k == 1 ? a.z : a.w;
+  uint32_t raw = (lo >> 16) | (hi << 16);
+  f.sport = bswap16(raw & 0xFFFFu);
+  f.dport = bswap16(raw >> 16);
+  f.ports = true;
+  return f;
+}
+
+/* mac_state of the entry of `ip`, or 0: nobody quarantines that address */
+BNG_DEV uint64_t wg_lookup(const bng_wg_entry* __restrict__ t, uint32_t mask,
+                           uint32_t ip) {
+  uint64_t key = BNG_WG_KEY(ip);
+  uint32_t slot = (uint32_t)bng_mix64(key) & mask;
+  for (int i = 0; i < BNG_MAX_PROBE; ++i) {
+    uint4 e = ld_probe16(&t[(slot + i) & mask]);
+    uint64_t k = ((uint64_t)e.y << 32) | e.x;
+    if (k == key) return ((uint64_t)e.w << 32) | e.z;
+    if (k == BNG_KEY_EMPTY) return 0;
+  }
+  return 0;
+}
+
+/* Membership in the sorted allow-list (at most 64 keys, L2-resident):
+ * (ip, port, proto) when the frame has readable ports, else the bare
+ * address. */
+BNG_DEV bool wg_allowed(const bng_wg_config* __restrict__ cfg, bool ports,
+                        uint32_t ip, uint32_t port, uint32_t proto) {
+  if (ports) {
+    uint64_t key = ((uint64_t)ip << 32) | ((uint64_t)port << 16) | proto;
+    uint32_t n = cfg->n_allowed;
+    int lo = 0, hi = (int)(n < BNG_MAX_WG_ALLOWED ? n : BNG_MAX_WG_ALLOWED);
+    while (lo < hi) {
+      int mid = (lo + hi) >> 1;
+      uint64_t v = cfg->allowed_key[mid];
+      if (v == key) return true;
+      if (v < key) lo = mid + 1; else hi = mid;
+    }
+    return false;
+  }
+  uint32_t n = cfg->n_allowed_ips;
+  int lo = 0, hi = (int)(n < BNG_MAX_WG_ALLOWED ? n : BNG_MAX_WG_ALLOWED);
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    uint32_t v = cfg->allowed_ip[mid];
+    if (v == ip) return true;
+    if (v < ip) lo = mid + 1; else hi = mid;
+  }
+  return false;
+}
+
+BNG_DEV bool wg_redirects(const bng_wg_config* __restrict__ cfg,
+                          uint32_t port) {
+  uint32_t n = cfg->n_redirect_ports;
+  if (n > BNG_MAX_WG_REDIRECT_PORTS) n = BNG_MAX_WG_REDIRECT_PORTS;
+  for (uint32_t i = 0; i < n; ++i)
+    if (cfg->redirect_port[i] == port) return true;
+  return false;
+}
+
+/* Uplink pre-pass: after pppoe_decap and acct_resolve, before the
+ * pipeline.  Position i handles packet order_in[i] (i without an order) and
+ * writes order_out[i]: the packet id, or -1 for a frame the gate decided —
+ * the pipeline skips an order entry outside [0, n) before it reads or
+ * writes anything, so such a frame never reaches antispoof, NAT or QoS.
+ * gate[] is written for every packet, verdict[] and out_len[] only for the
+ * decided ones.  No lane leaves an iteration early: every lane reaches the
+ * wave-wide stat counts. */
+__global__ __launch_bounds__(256)
+void wg_uplink_kernel(const uint8_t* __restrict__ data,
+                      const uint16_t* __restrict__ in_len,
+                      uint8_t* __restrict__ verdict,
+                      uint16_t* __restrict__ out_len,
+                      uint8_t* __restrict__ gate,
+                      const int32_t* __restrict__ order_in,
+                      int32_t* __restrict__ order_out, int n, int stride,
+                      const bng_wg_entry* __restrict__ table, uint32_t mask,
+                      const bng_wg_config* __restrict__ cfg,
+                      unsigned long long* stats) {
+  __shared__ unsigned long long sb[BNG_WG_NSTATS];
+  sb_zero(sb, BNG_WG_NSTATS);
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int i = base + tid;
+    uint32_t g = BNG_WG_NONE;
+    if (i < n) do {
+      int pid = order_in ? order_in[i] : i;
+      if ((unsigned)pid >= (unsigned)n) {            /* not ours to judge */
+        order_out[i] = pid;
+        break;
+      }
+      int len = in_len[pid];
+      wg_frame f = wg_parse(data + (size_t)pid * stride, len, stride);
+      uint64_t ms = f.eligible ? wg_lookup(table, mask, f.saddr) : 0;
+      uint32_t state = (uint32_t)(ms >> BNG_WG_STATE_SHIFT);
+      uint8_t v = BNG_DROP;
+      if (state == BNG_WG_BLOCKED) {
+        g = BNG_WG_DROP_BLOCKED;
+      } else if (state != BNG_WG_WALLED) {
+        g = BNG_WG_NONE;
+      } else if ((ms & BNG_WG_MAC_MASK) != f.smac) {
+        g = BNG_WG_DROP_MAC;                         /* the gate's uRPF */
+      } else if (f.ports && f.proto == 17 && f.dport == 67) {
+        g = BNG_WG_NONE;                             /* a lease renewal */
+      } else if (wg_allowed(cfg, f.ports, f.daddr, f.dport, f.proto)) {
+        g = BNG_WG_ALLOW; v = BNG_FWD;
+      } else if (f.ports && f.proto == 6 && wg_redirects(cfg, f.dport)) {
+        g = BNG_WG_REDIRECT; v = BNG_PASS;
+      } else {
+        g = BNG_WG_DROP_WALLED;
+      }
+      gate[pid] = (uint8_t)g;
+      if (g != BNG_WG_NONE) {
+        verdict[pid] = v;
+        out_len[pid] = (uint16_t)len;
+      }
+      order_out[i] = g != BNG_WG_NONE ? -1 : pid;
+    } while (0);
+    sb_fold(sb, BNG_WS_UP_ALLOWED, wave_count(g == BNG_WG_ALLOW));
+    sb_fold(sb, BNG_WS_UP_REDIRECTED, wave_count(g == BNG_WG_REDIRECT));
+    sb_fold(sb, BNG_WS_UP_DROP_WALLED, wave_count(g == BNG_WG_DROP_WALLED));
+    sb_fold(sb, BNG_WS_UP_DROP_BLOCKED, wave_count(g == BNG_WG_DROP_BLOCKED));
+    sb_fold(sb, BNG_WS_UP_DROP_MAC, wave_count(g == BNG_WG_DROP_MAC));
+  }
+  __syncthreads();
+  sb_commit(sb, 0, BNG_WG_NSTATS, stats);
+}
+
+/* Downlink post-pass: after the pipeline, before acct_downlink and
+ * pppoe_encap.  Only a forwarded, eligible frame whose (DNAT-rewritten)
+ * destination is in the garden is judged; the gate can only turn FWD into
+ * DROP. */
+__global__ __launch_bounds__(256)
+void wg_downlink_kernel(const uint8_t* __restrict__ data,
+                        const uint16_t* __restrict__ in_len,
+                        uint8_t* __restrict__ verdict,
+                        uint8_t* __restrict__ gate, int n, int stride,
+                        const bng_wg_entry* __restrict__ table,
+                        uint32_t mask,
+                        const bng_wg_config* __restrict__ cfg,
+                        unsigned long long* stats) {
+  __shared__ unsigned long long sb[BNG_WG_NSTATS];
+  sb_zero(sb, BNG_WG_NSTATS);
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int nthreads = gridDim.x * blockDim.x;
+  for (int base = 0; base < n; base += nthreads) {
+    int pid = base + tid;
+    uint32_t g = BNG_WG_NONE;
+    if (pid < n) do {
+      if (verdict[pid] != BNG_FWD) { gate[pid] = BNG_WG_NONE; break; }
+      wg_frame f = wg_parse(data + (size_t)pid * stride, in_len[pid],
+                            stride);
+      uint64_t ms = f.eligible ? wg_lookup(table, mask, f.daddr) : 0;
+      uint32_t state = (uint32_t)(ms >> BNG_WG_STATE_SHIFT);
+      if (state == BNG_WG_BLOCKED) {
+        g = BNG_WG_DROP_BLOCKED;
+      } else if (state != BNG_WG_WALLED) {
+        g = BNG_WG_NONE;
+      } else if (wg_allowed(cfg, f.ports, f.saddr, f.sport, f.proto)) {
+        g = BNG_WG_ALLOW;
+      } else {
+        g = BNG_WG_DROP_WALLED;
+      }
+      gate[pid] = (uint8_t)g;
+      if (g == BNG_WG_DROP_WALLED || g == BNG_WG_DROP_BLOCKED)
+        verdict[pid] = (uint8_t)BNG_DROP;
+    } while (0);
+    sb_fold(sb, BNG_WS_DOWN_ALLOWED, wave_count(g == BNG_WG_ALLOW));
+    sb_fold(sb, BNG_WS_DOWN_DROP_WALLED,
+            wave_count(g == BNG_WG_DROP_WALLED));
+    sb_fold(sb, BNG_WS_DOWN_DROP_BLOCKED,
+            wave_count(g == BNG_WG_DROP_BLOCKED));
+  }
+  __syncthreads();
+  sb_commit(sb, 0, BNG_WG_NSTATS, stats);
+}
+
+/* Stream-ordered entry CRUD, one thread per batch record, under the batch
+ * contract of the host CRUD probes: a batch must not name the same address
+ * twice.  An upsert of a live address replaces its MAC and state in place;
+ * the batch records carry the key already (BNG_WG_KEY of the address). */
+__global__ void wg_upsert_kernel(bng_wg_entry* t, uint32_t mask,
+                                 const bng_wg_entry* __restrict__ batch,
+                                 int n, int* rc) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bng_wg_entry r = batch[i];
+  bng_wg_entry* e = key_upsert_slot<&bng_wg_entry::key>(t, mask, r.key);
+  if (!e) { rc[i] = -1; return; }
+  rlx_store64(&e->mac_state, r.mac_state);
+  rc[i] = 0;
+}
+
+__global__ void wg_delete_kernel(bng_wg_entry* t, uint32_t mask,
+                                 const uint32_t* __restrict__ ips, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bng_wg_entry* e =
+      key_find<&bng_wg_entry::key>(t, mask, BNG_WG_KEY(ips[i]));
+  if (e) rlx_store64(&e->key, BNG_KEY_TOMBSTONE);
+}
+
 /* ============================= extern "C" launchers for the extension */
 
 /* Grid cap of the six batched packet kernels (grid-stride above it).
@@ -3226,6 +3489,41 @@ void bng_launch_acct_delete(void* table, uint32_t mask, const void* ips,
   hipLaunchKernelGGL(acct_delete_kernel, dim3((n + 255) / 256), dim3(256), 0,
       s, (bng_acct_entry*)table, mask, (const uint32_t*)ips, n,
       (bng_acct_entry*)out);
+}
+
+void bng_launch_wg_uplink(const void* data, const void* in_len,
+                          void* verdict, void* out_len, void* gate,
+                          const void* order_in, void* order_out, int n,
+                          int stride, const void* table, uint32_t mask,
+                          const void* cfg, void* stats, hipStream_t s) {
+  hipLaunchKernelGGL(wg_uplink_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (const uint8_t*)data, (const uint16_t*)in_len, (uint8_t*)verdict,
+      (uint16_t*)out_len, (uint8_t*)gate, (const int32_t*)order_in,
+      (int32_t*)order_out, n, stride, (const bng_wg_entry*)table, mask,
+      (const bng_wg_config*)cfg, (unsigned long long*)stats);
+}
+
+void bng_launch_wg_downlink(const void* data, const void* in_len,
+                            void* verdict, void* gate, int n, int stride,
+                            const void* table, uint32_t mask,
+                            const void* cfg, void* stats, hipStream_t s) {
+  hipLaunchKernelGGL(wg_downlink_kernel, dim3(pkt_grid(n)), dim3(256), 0, s,
+      (const uint8_t*)data, (const uint16_t*)in_len, (uint8_t*)verdict,
+      (uint8_t*)gate, n, stride, (const bng_wg_entry*)table, mask,
+      (const bng_wg_config*)cfg, (unsigned long long*)stats);
+}
+
+void bng_launch_wg_upsert(void* table, uint32_t mask, const void* batch,
+                          int n, void* rc, hipStream_t s) {
+  hipLaunchKernelGGL(wg_upsert_kernel, dim3((n + 255) / 256), dim3(256), 0,
+      s, (bng_wg_entry*)table, mask, (const bng_wg_entry*)batch, n,
+      (int*)rc);
+}
+
+void bng_launch_wg_delete(void* table, uint32_t mask, const void* ips, int n,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(wg_delete_kernel, dim3((n + 255) / 256), dim3(256), 0,
+      s, (bng_wg_entry*)table, mask, (const uint32_t*)ips, n);
 }
 
 void bng_launch_shard_owner(const void* data, const void* in_len,

@@ -86,6 +86,17 @@ void bng_launch_acct_read(void* table, uint32_t mask, const void* ips, int n,
     void* out, hipStream_t s);
 void bng_launch_acct_delete(void* table, uint32_t mask, const void* ips,
     int n, void* out, hipStream_t s);
+void bng_launch_wg_uplink(const void* data, const void* in_len, void* verdict,
+    void* out_len, void* gate, const void* order_in, void* order_out, int n,
+    int stride, const void* table, uint32_t mask, const void* cfg,
+    void* stats, hipStream_t s);
+void bng_launch_wg_downlink(const void* data, const void* in_len,
+    void* verdict, void* gate, int n, int stride, const void* table,
+    uint32_t mask, const void* cfg, void* stats, hipStream_t s);
+void bng_launch_wg_upsert(void* table, uint32_t mask, const void* batch,
+    int n, void* rc, hipStream_t s);
+void bng_launch_wg_delete(void* table, uint32_t mask, const void* ips, int n,
+    hipStream_t s);
 
 } /* extern "C" */
 

@@ -186,6 +186,13 @@ class GoldenDataplane:
         self.pppoe_stats = [0] * abi.PPPOE_NSTATS
         # per-subscriber traffic accounting, by subscriber IPv4
         self.acct: Dict[int, AcctRec] = {}
+        # walled-garden gate: subscriber IPv4 -> (mac as u64, abi.WG_*
+        # state), and what a quarantined subscriber may reach
+        self.wg: Dict[int, Tuple[int, int]] = {}
+        self.wg_allowed: set = set()          # (ip, port, proto)
+        self.wg_allowed_ips: set = set()      # the addresses of those keys
+        self.wg_redirect_ports: set = set(abi.WG_DEFAULT_REDIRECT_PORTS)
+        self.wg_stats = [0] * abi.WG_NSTATS
 
     # ------------------------------------------------------------- helpers
     @property
@@ -851,6 +858,120 @@ class GoldenDataplane:
                 e.up_drop_pkts += 1
             else:
                 e.down_drop_pkts += 1
+
+    # ================================================ walled-garden gate
+    def wg_set_config(self, allowed, redirect_ports=None):
+        """The allow-list as (ip, port, proto) ints and the TCP ports whose
+        traffic goes to the host for the portal redirect."""
+        keys, ips, ports = abi.wg_fold_config(
+            allowed, abi.WG_DEFAULT_REDIRECT_PORTS
+            if redirect_ports is None else redirect_ports)
+        self.wg_allowed = {(k >> 32, (k >> 16) & 0xFFFF, k & 0xFF)
+                           for k in keys}
+        self.wg_allowed_ips = set(ips)
+        self.wg_redirect_ports = set(ports)
+
+    def _garden_parse(self, frame) -> Optional[dict]:
+        """None: the gate does not judge this frame (shorter than 34 B,
+        tagged or not IPv4, version != 4, ihl < 5).  `ports`: TCP or UDP,
+        first fragment, and the frame holds the whole TCP (20 B) / UDP
+        (8 B) header, wherever IP options put it; every other frame is
+        portless (another protocol, ICMP included, a non-first fragment, a
+        truncated L4 header)."""
+        n = len(frame)
+        if n < 34 or struct.unpack_from(">H", frame, 12)[0] != ETH_P_IP:
+            return None
+        if not self._ipv4_header_ok(frame, 14):
+            return None
+        proto = frame[23]
+        saddr, daddr = struct.unpack_from(">II", frame, 26)
+        l4 = 14 + (frame[14] & 0xF) * 4
+        r = dict(saddr=saddr, daddr=daddr, proto=proto, ports=False,
+                 sport=0, dport=0, smac=abi.mac_to_u64(bytes(frame[6:12])))
+        frag = struct.unpack_from(">H", frame, 20)[0] & 0x1FFF
+        if proto in (6, 17) and not frag and \
+                n >= l4 + (20 if proto == 6 else 8):
+            r["sport"], r["dport"] = struct.unpack_from(">HH", frame, l4)
+            r["ports"] = True
+        return r
+
+    def _garden_allowed(self, h: dict, ip: int, port: int) -> bool:
+        if h["ports"]:
+            return (ip, port, h["proto"]) in self.wg_allowed
+        return ip in self.wg_allowed_ips
+
+    def garden_uplink(self, frame) -> Tuple[int, Optional[int]]:
+        """The uplink gate's decision for one frame, keyed on its source
+        address (wg_uplink_kernel): (gate code, verdict).  Gate NONE has
+        verdict None — the pipeline decides, as without a garden; every
+        other gate fixes the verdict, the frame keeps its bytes and length
+        and never enters the pipeline.  In table order:
+
+          not judged, or source not in the garden      NONE
+          entry BLOCKED                                DROP_BLOCKED  DROP
+          WALLED, source MAC is not the entry's        DROP_MAC      DROP
+          WALLED, UDP to port 67 (a lease renewal)     NONE
+          WALLED, (daddr, dport, proto) allow-listed   ALLOW         FWD
+          WALLED, TCP to a redirect port               REDIRECT      PASS
+          WALLED, portless, daddr allow-listed         ALLOW         FWD
+          WALLED, anything else                        DROP_WALLED   DROP
+
+        ALLOW forwards without NAT: the portal and its resolvers sit inside
+        the operator's network.  The last four rows are Manager.classify()
+        with port 0 for a portless frame; a frame with readable ports to
+        port 0 is the one place they differ (classify takes port 0 as "no
+        port", the gate looks (daddr, 0, proto) up and drops)."""
+        h = self._garden_parse(frame)
+        e = self.wg.get(h["saddr"]) if h is not None else None
+        if e is None:
+            return abi.WG_NONE, None
+        mac, state = e
+        st = self.wg_stats
+        if state == abi.WG_BLOCKED:
+            st[abi.WS_UP_DROP_BLOCKED] += 1
+            return abi.WG_DROP_BLOCKED, DROP
+        if state != abi.WG_WALLED:
+            return abi.WG_NONE, None
+        if h["smac"] != mac:
+            st[abi.WS_UP_DROP_MAC] += 1
+            return abi.WG_DROP_MAC, DROP
+        if h["ports"] and h["proto"] == 17 and h["dport"] == 67:
+            return abi.WG_NONE, None
+        if self._garden_allowed(h, h["daddr"], h["dport"]):
+            st[abi.WS_UP_ALLOWED] += 1
+            return abi.WG_ALLOW, FWD
+        if h["ports"] and h["proto"] == 6 and \
+                h["dport"] in self.wg_redirect_ports:
+            st[abi.WS_UP_REDIRECTED] += 1
+            return abi.WG_REDIRECT, PASS
+        st[abi.WS_UP_DROP_WALLED] += 1
+        return abi.WG_DROP_WALLED, DROP
+
+    def garden_downlink(self, frame, verdict: int) -> Tuple[int, int]:
+        """The downlink gate (wg_downlink_kernel), after the pipeline: a
+        forwarded frame whose DNAT-rewritten destination is in the garden
+        stays FWD only if the entry is WALLED and its source is
+        allow-listed — (saddr, sport, proto), or the bare address for a
+        portless frame.  Returns (gate code, verdict); the gate can only
+        turn FWD into DROP."""
+        if verdict != FWD:
+            return abi.WG_NONE, verdict
+        h = self._garden_parse(frame)
+        e = self.wg.get(h["daddr"]) if h is not None else None
+        if e is None:
+            return abi.WG_NONE, verdict
+        _mac, state = e
+        st = self.wg_stats
+        if state == abi.WG_BLOCKED:
+            st[abi.WS_DOWN_DROP_BLOCKED] += 1
+            return abi.WG_DROP_BLOCKED, DROP
+        if state != abi.WG_WALLED:
+            return abi.WG_NONE, verdict
+        if self._garden_allowed(h, h["saddr"], h["sport"]):
+            st[abi.WS_DOWN_ALLOWED] += 1
+            return abi.WG_ALLOW, FWD
+        st[abi.WS_DOWN_DROP_WALLED] += 1
+        return abi.WG_DROP_WALLED, DROP
 
     # ====================================================== antispoof K4
     def antispoof(self, frame: bytes) -> int:

@@ -40,6 +40,20 @@ def _struct_bytes(s: ctypes.Structure) -> bytes:
     return ctypes.string_at(ctypes.addressof(s), ctypes.sizeof(s))
 
 
+def _wg_records(entries) -> List[Tuple[int, int, int]]:
+    """(ip, mac as u64, state) records of a wg_set batch, checked."""
+    recs = []
+    for ip, mac, state in entries:
+        if state not in (abi.WG_WALLED, abi.WG_BLOCKED):
+            raise ValueError(f"walled-garden state must be WG_WALLED or "
+                             f"WG_BLOCKED, got {state!r}")
+        m = mac if isinstance(mac, int) else abi.mac_to_u64(bytes(mac))
+        recs.append((int(ip) & 0xFFFFFFFF, m & abi.WG_MAC_MASK, state))
+    if len({r[0] for r in recs}) != len(recs):
+        raise ValueError("a walled-garden batch must not repeat an address")
+    return recs
+
+
 class HipLauncher:
     """GPU-backed dataplane for one shard."""
 
@@ -48,7 +62,8 @@ class HipLauncher:
                  subnat_log2: int = 18, qos_log2: int = 18,
                  binding_log2: int = 18, n_pools: int = 1024,
                  svc_cus: int = 0, pppoe_log2: int = 17,
-                 acct_log2: int = abi.MAX_ACCT_LOG2):
+                 acct_log2: int = abi.MAX_ACCT_LOG2,
+                 wg_log2: int = abi.MAX_WG_LOG2):
         import torch
         from .build import get_ext
         self.torch = torch
@@ -121,11 +136,24 @@ class HipLauncher:
         self._acct_slot = None
         self._acct_live: set = set()
         self.acct_launches = {"resolve": 0, "commit": 0, "downlink": 0}
+        # walled-garden gate: the table (2^wg_log2 16-B entries) exists
+        # from the first wg_set on; while no entry is live uplink() and
+        # downlink() launch exactly what they launched before the gate
+        # existed.  wg_launches counts the gate kernels they did launch.
+        self.wg_log2 = wg_log2
+        self.wg = None
+        self.wg_cfg = z(ctypes.sizeof(abi.WgConfig))
+        self.wg_stats = torch.zeros(abi.WG_NSTATS, dtype=torch.int64,
+                                    device=self.device)
+        self._wg_live: Dict[int, Tuple[int, int]] = {}
+        self.wg_launches = {"uplink": 0, "downlink": 0}
+        self.last_wg_gate = None
         # host-side circuit-id collision registry (ref loader.go:519-608)
         self._circuit_ids: Dict[int, bytes] = {}
         # defaults
         self.set_nat_config()
         self.set_antispoof_config()
+        self.wg_set_config(())
 
     # ------------------------------------------------------------ helpers
     def _to_dev(self, raw: bytes):
@@ -537,6 +565,83 @@ class HipLauncher:
                 max(n, 8192), dtype=self.torch.int32, device=self.device)
         return self._acct_slot
 
+    # ============================================== walled-garden gate
+    def wg_set_config(self, allowed, redirect_ports=(80, 8080)):
+        """What a quarantined subscriber may reach: `allowed` is an
+        iterable of (ip, port, proto) ints (duplicates fold), TCP to a
+        `redirect_ports` port goes to the host for the portal redirect.
+        More than 64 keys or 8 ports is a ValueError."""
+        keys, ips, ports = abi.wg_fold_config(allowed, redirect_ports)
+        c = abi.WgConfig(n_allowed=len(keys), n_allowed_ips=len(ips),
+                         n_redirect_ports=len(ports))
+        for i, k in enumerate(keys):
+            c.allowed_key[i] = k
+        for i, ip in enumerate(ips):
+            c.allowed_ip[i] = ip
+        for i, p in enumerate(ports):
+            c.redirect_port[i] = p
+        self.wg_cfg.copy_(self._to_dev(_struct_bytes(c)))
+
+    def wg_set(self, entries):
+        """Put subscriber addresses into the garden, or change the MAC /
+        state of ones already there, in place: `entries` is an iterable of
+        (ip, mac, state) with state abi.WG_WALLED or abi.WG_BLOCKED.  One
+        launch; a batch must not repeat an address."""
+        import numpy as np
+        recs = _wg_records(entries)
+        if not recs:
+            return
+        if self.wg is None:
+            self.wg = self.torch.zeros((1 << self.wg_log2) * 16,
+                                       dtype=self.torch.uint8,
+                                       device=self.device)
+        arr = np.array([(abi.wg_key(ip), abi.wg_mac_state(mac, st))
+                        for ip, mac, st in recs], dtype=abi.WG_ENTRY_DTYPE)
+        batch = self.torch.from_numpy(arr.view(np.uint8)).to(self.device)
+        rc = self.torch.zeros(len(recs), dtype=self.torch.int32,
+                              device=self.device)
+        self.ext.wg_upsert(self.wg, batch, rc)
+        # quarantine is a control-plane event: pay the sync and keep the
+        # host-side set of live entries exact
+        bad = (rc != 0).cpu().numpy()
+        for (ip, mac, st), failed in zip(recs, bad):
+            if not failed:
+                self._wg_live[ip] = (mac, st)
+        if bad.any():
+            raise RuntimeError(
+                f"walled-garden table full: {int(bad.sum())} subscriber(s) "
+                f"not gated (raise wg_log2, now {self.wg_log2})")
+
+    def wg_remove(self, ips):
+        """Release addresses from the garden (activation, removal, TTL
+        expiry); an address not in it is ignored."""
+        import numpy as np
+        arr = np.asarray(sorted({int(ip) & 0xFFFFFFFF for ip in ips}),
+                         dtype=np.uint32)
+        if self.wg is None or not len(arr):
+            return
+        self.ext.wg_delete(
+            self.wg, self.torch.from_numpy(arr.view(np.int32)).to(self.device))
+        for ip in arr.tolist():
+            self._wg_live.pop(ip, None)
+
+    def wg_export(self):
+        """Every live entry as WG_ENTRY_DTYPE records, from a host-side
+        view of the table blob."""
+        import numpy as np
+        if self.wg is None:
+            return np.zeros(0, dtype=abi.WG_ENTRY_DTYPE)
+        arr = self.wg.cpu().numpy().view(np.dtype(abi.WG_ENTRY_DTYPE))
+        return arr[(arr["key"] != 0) &
+                   (arr["key"] != 0xFFFFFFFFFFFFFFFF)].copy()
+
+    @property
+    def wg_count(self) -> int:
+        return len(self._wg_live)
+
+    def wg_get_stats(self) -> Dict[str, int]:
+        return dict(zip(abi.WG_STAT_NAMES, self.wg_stats.cpu().tolist()))
+
     # ================================================ batched processing
     def make_batch(self, frames: Sequence[bytes], stride: int = 512):
         """Pack frames into a device batch (data[n,stride], len[n])."""
@@ -614,7 +719,13 @@ class HipLauncher:
         state stays reachable as last_pppoe_state.
 
         With accounting entries live (acct_add), acct_resolve runs after
-        the decap and acct_commit last of all, on the final verdicts."""
+        the decap and acct_commit last of all, on the final verdicts.
+
+        With garden entries live (wg_set), the walled-garden gate runs
+        after acct_resolve and the type sort: it fixes the verdict of every
+        frame of a quarantined or blocked subscriber and hands the pipeline
+        an order without them.  The per-packet gate codes (abi.WG_*) stay
+        reachable as last_wg_gate; acct_commit bills ALLOW like any FWD."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
@@ -632,6 +743,19 @@ class HipLauncher:
                                    device=self.device)
             self.ext.pkt_class(data, lens, cls)
             order = self.torch.argsort(cls, stable=True).to(self.torch.int32)
+        # walled-garden gate: the frames it decides leave the dispatch
+        # order, so they never reach antispoof, NAT or QoS
+        if self._wg_live and n:
+            gate = self.torch.zeros(n, dtype=self.torch.uint8,
+                                    device=self.device)
+            order_out = self.torch.empty(n, dtype=self.torch.int32,
+                                         device=self.device)
+            self.ext.wg_uplink(data, lens, verdict, out_len, gate, order,
+                               order_out, self.wg, self.wg_cfg,
+                               self.wg_stats)
+            self.wg_launches["uplink"] += 1
+            self.last_wg_gate = gate
+            order = order_out
         self.ext.uplink_pipeline(
             data, lens, out_len, verdict, self.subs, self.pools,
             self.server_cfg, self.dhcp_stats, self.bindings, self.as_cfg,
@@ -653,7 +777,10 @@ class HipLauncher:
         """Fused NAT44 DNAT -> QoS-egress return path.  With PPPoE sessions
         provisioned, pppoe_encap() follows: `lens` is updated in place and
         the state stays reachable as last_pppoe_state.  With accounting
-        entries live, acct_downlink bills the frames in between."""
+        entries live, acct_downlink bills the frames in between.  With
+        garden entries live, the walled-garden gate runs right behind the
+        pipeline and turns FWD into DROP for what a quarantined or blocked
+        subscriber may not receive (last_wg_gate)."""
         n = lens.numel()
         verdict, out_len = self._outs(n)
         now = now_ns if now_ns is not None else time.time_ns()
@@ -666,6 +793,13 @@ class HipLauncher:
             self.nat_log_hdr, self.qos_egress, self.qos_stats, now,
             now // 10**9, order=None, downlink=True,
             masked=self.masked_compute)
+        if self._wg_live and n:
+            gate = self.torch.empty(n, dtype=self.torch.uint8,
+                                    device=self.device)
+            self.ext.wg_downlink(data, lens, verdict, gate, self.wg,
+                                 self.wg_cfg, self.wg_stats)
+            self.wg_launches["downlink"] += 1
+            self.last_wg_gate = gate
         if self._acct_live and n:
             # before the encap: both directions count the IPoE length
             self.ext.acct_downlink(data, lens, verdict, self.acct, now)
@@ -1144,6 +1278,32 @@ class GoldenLauncher:
     def acct_count(self):
         return len(self.dp.acct)
 
+    # walled-garden gate (same surface as HipLauncher's; the model has no
+    # capacity, so wg_log2 is accepted and never reached)
+    def wg_set_config(self, allowed, redirect_ports=(80, 8080)):
+        self.dp.wg_set_config(allowed, redirect_ports)
+
+    def wg_set(self, entries):
+        for ip, mac, state in _wg_records(entries):
+            self.dp.wg[ip] = (mac, state)
+
+    def wg_remove(self, ips):
+        for ip in ips:
+            self.dp.wg.pop(int(ip) & 0xFFFFFFFF, None)
+
+    def wg_export(self):
+        import numpy as np
+        return np.array([(abi.wg_key(ip), abi.wg_mac_state(mac, st))
+                         for ip, (mac, st) in self.dp.wg.items()],
+                        dtype=abi.WG_ENTRY_DTYPE)
+
+    @property
+    def wg_count(self):
+        return len(self.dp.wg)
+
+    def wg_get_stats(self):
+        return dict(zip(abi.WG_STAT_NAMES, self.dp.wg_stats))
+
     # processing (frames as list[bytearray]); mirrors HipLauncher outputs
     def process_dhcp(self, frames, now_sec=None):
         if now_sec is not None:
@@ -1240,7 +1400,9 @@ class CapturedUplink:
     """hipGraph replay wrapper for the fused uplink pipeline.
 
     The PPPoE session-data pre-pass is not part of the captured sequence:
-    PPPoE data frames replayed through it PASS to the host as before."""
+    PPPoE data frames replayed through it PASS to the host as before.
+    The walled-garden gate, like the PPPoE pre-pass, is not part of the
+    captured sequence."""
 
     def __init__(self, launcher: HipLauncher, n: int, stride: int,
                  sort_by_type: bool):

@@ -402,12 +402,18 @@ class Pump:
                 # two uplink passes: keyed on the source before SNAT
                 # rewrites it, billed by the chain's verdict
                 akey = dp.acct_resolve(fr, "src") if dp.acct else None
-                vd = self.launcher.dp.antispoof(bytes(fr))
-                if vd == abi.FWD:
-                    fb = bytearray(fr)
-                    vd = self.launcher.dp.nat44_egress(fb)
+                # walled-garden gate, where HipLauncher.uplink runs it: a
+                # frame it decides skips the stage chain; ALLOW goes out
+                # untouched, REDIRECT goes to the host
+                gate, vd = dp.garden_uplink(fr) if dp.wg \
+                    else (abi.WG_NONE, None)
+                fb = bytearray(fr)
+                if gate == abi.WG_NONE:
+                    vd = self.launcher.dp.antispoof(bytes(fr))
                     if vd == abi.FWD:
-                        vd = self.launcher.dp.qos(bytes(fb), "ingress")
+                        vd = self.launcher.dp.nat44_egress(fb)
+                        if vd == abi.FWD:
+                            vd = self.launcher.dp.qos(bytes(fb), "ingress")
                 dp.acct_commit(akey, "uplink", len(fr), vd, dp.now_ns)
                 if vd == abi.FWD:
                     out_frames.append(bytes(fb))
@@ -483,6 +489,10 @@ class Pump:
             if vd == abi.FWD:
                 vd = self.launcher.dp.qos(bytes(fb), "egress")
             dp = self.launcher.dp
+            if dp.wg:
+                # walled-garden gate: FWD -> DROP for what a quarantined
+                # or blocked subscriber may not receive
+                _gate, vd = dp.garden_downlink(fb, vd)
             if dp.acct:
                 # keyed on the DNAT-rewritten destination, before the encap
                 dp.acct_commit(dp.acct_resolve(fb, "dst"), "downlink",

@@ -183,6 +183,9 @@ class Metrics:
                 for name, v in launcher.pppoe_get_stats().items():
                     self.dataplane_stat.labels("pppoe", name).set(v)
                     self.pppoe_fastpath[name].set(v)
+            if hasattr(launcher, "wg_get_stats"):
+                for name, v in launcher.wg_get_stats().items():
+                    self.dataplane_stat.labels("walledgarden", name).set(v)
             if getattr(launcher, "acct_count", 0):
                 self._collect_session_bytes(launcher.acct_export())
         if dhcp_server is not None:

@@ -4,7 +4,10 @@ blocked (:16-44), allowed destinations (DNS/portal), TTL expiry checker
 (:347-396).  Like the reference (which has no walled_garden.c — the
 redirect exists only in docs), enforcement hooks are optional: the
 manager keeps authoritative state and can push allow-lists into the
-dataplane via set_dataplane_hooks."""
+dataplane via set_dataplane_hooks.  walledgarden/dataplane.py is that
+push: it keeps a launcher's gate table and allow-list in step with this
+state machine, and the gate kernels enforce classify()'s table on the
+packet path."""
 from __future__ import annotations
 
 import threading
@@ -59,6 +62,7 @@ class Manager:
         self._lock = threading.RLock()
         self._hooks: List[Callable[[Entry], None]] = []
         self._redirect_cbs: List[Callable[[str, str], None]] = []
+        self._dest_cbs: List[Callable[[], None]] = []
         self._stop = threading.Event()
         self._checker: Optional[threading.Thread] = None
         self.stats = {"added": 0, "activated": 0, "blocked": 0,
@@ -143,6 +147,16 @@ class Manager:
         self.allowed_dests[(ip, port, proto)] = reason
         if ip not in self.allowed_destinations:
             self.allowed_destinations.append(ip)
+        for cb in self._dest_cbs:
+            try:
+                cb()
+            except Exception:
+                pass
+
+    def on_destinations_changed(self, cb: Callable[[], None]):
+        """cb() after every allow_destination, so a dataplane that holds a
+        copy of allowed_dests can follow it."""
+        self._dest_cbs.append(cb)
 
     def on_redirect(self, cb: Callable[[str, str], None]):
         """cb(mac, dst_ip) whenever quarantined HTTP gets redirected
