@@ -1221,19 +1221,42 @@ BNG_DEV void nat_log_push(const nat_tables& T, uint32_t ev, uint32_t sub_id,
   e->protocol = proto; e->flags = flags;
 }
 
-/* Port rotor (ref allocate_port_from_block nat44.c:408-466): atomic
- * next_port bump, wrap, optional RTP parity, EIM-collision heuristic.
- * The reference's wrap is a tolerated benign race; ours keeps it. */
+/* Port rotor (ref allocate_port_from_block nat44.c:408-466): take the
+ * rotor's position, step it with the wrap, optional RTP parity,
+ * EIM-collision heuristic.
+ *
+ * Position and wrap are ONE compare-and-swap on next_port.  The reference
+ * bumps the counter and repairs the wrap afterwards, a race two CPUs have
+ * to collide on; here the lanes of a wave get consecutive counter values
+ * in lock-step, so every wave that crossed port_end handed port_start to
+ * all of its lanes past the end (and, in a block ending at 65535, the
+ * counter truncated to 16 bits came out as port 0 = "exhausted", then as
+ * ports 1, 2, ... outside the block).  With the CAS k <= block-size
+ * concurrent callers get k consecutive positions modulo the block size,
+ * next_port never leaves [port_start, port_end], and any interleaving
+ * gives what the sequential model gives.  The loop is lock-free: a failed
+ * CAS means another caller's landed, so the retries of one caller are
+ * bounded by the callers racing it, and the failed CAS returns the value
+ * to retry with.  Only the session-create path comes here. */
 BNG_DEV uint16_t nat_alloc_port(const nat_tables& T, bng_subctx* blk,
                                 bool parity, uint16_t orig_port,
                                 uint32_t internal_ip, uint8_t proto) {
   uint8_t orig_parity = orig_port & 1;
+  const uint32_t first = blk->port_start, last = blk->port_end;
+  uint32_t cur = rlx_load32(&blk->next_port);
   for (int i = 0; i < 64; ++i) {
-    uint32_t r = atomicAdd(&blk->next_port, 1u);
-    uint16_t port = (uint16_t)r;
-    if (port > blk->port_end) port = blk->port_start;
-    if (r + 1 > blk->port_end)
-      atomicCAS(&blk->next_port, r + 1, (uint32_t)blk->port_start);
+    uint32_t pos, nxt;
+    for (;;) {
+      /* a position outside the block (a table image from elsewhere)
+       * restarts the rotor instead of being handed out */
+      pos = (cur >= first && cur <= last) ? cur : first;
+      nxt = pos == last ? first : pos + 1;
+      uint32_t seen = atomicCAS(&blk->next_port, cur, nxt);
+      if (seen == cur) break;
+      cur = seen;
+    }
+    cur = nxt;
+    uint16_t port = (uint16_t)pos;
     if (parity && (port & 1) != orig_parity) continue;
     uint64_t esig = bng_eim_sig(internal_ip, port, proto);
     bng_eim_entry* ex = sig_lookup(T.eim, T.eim_mask, esig);

@@ -43,6 +43,10 @@ class AccountingManager:
         self.sessions: Dict[str, SessionRecord] = {}
         self.pending: List[dict] = []   # failed sends awaiting retry
         self._lock = threading.RLock()
+        # orders the records of a session on the wire: an Interim-Update
+        # the interim thread picked before stop_session() ran must not go
+        # out after the Stop.  Held across one send at a time.
+        self._wire = threading.RLock()
         self._stop = threading.Event()
         self._threads: List[threading.Thread] = []
         self._counter_fetcher = None
@@ -112,15 +116,16 @@ class AccountingManager:
             rec = self.sessions.get(session_id)
         if rec is not None:
             self._refresh_counters(rec)
-        with self._lock:
-            rec = self.sessions.pop(session_id, None)
-        if rec is None:
-            return
-        rec.stopped = True
-        rec.terminate_cause = terminate_cause
-        self._persist()
-        if not self._try_send(rp.ACCT_STOP, rec):
-            self._queue(rp.ACCT_STOP, rec)
+        with self._wire:
+            with self._lock:
+                rec = self.sessions.pop(session_id, None)
+            if rec is None:
+                return
+            rec.stopped = True
+            rec.terminate_cause = terminate_cause
+            self._persist()
+            if not self._try_send(rp.ACCT_STOP, rec):
+                self._queue(rp.ACCT_STOP, rec)
 
     # ------------------------------------------------------------- sends
     def _try_send(self, status: int, rec: SessionRecord) -> bool:
@@ -145,7 +150,10 @@ class AccountingManager:
         self._persist()
 
     def _interim_loop(self):
-        while not self._stop.wait(min(self.interim_interval, 1.0)):
+        # tick well inside the interval: a tick as long as the interval
+        # itself lands just before a record falls due and sends it one
+        # whole interval late
+        while not self._stop.wait(min(self.interim_interval / 4, 1.0)):
             now = time.time()
             due = []
             with self._lock:
@@ -158,9 +166,12 @@ class AccountingManager:
                 self._send_interim(rec)
 
     def _send_interim(self, rec: SessionRecord):
-        self._refresh_counters(rec)
-        if not self._try_send(rp.ACCT_INTERIM, rec):
-            self._queue(rp.ACCT_INTERIM, rec)
+        with self._wire:
+            if rec.stopped:          # its Stop is out: nothing follows it
+                return
+            self._refresh_counters(rec)
+            if not self._try_send(rp.ACCT_INTERIM, rec):
+                self._queue(rp.ACCT_INTERIM, rec)
 
     def send_interim(self, session_id: str) -> bool:
         """An Interim-Update for one session now, outside the schedule

@@ -300,8 +300,12 @@ class TestNAT44:
 
     def test_port_exhaustion_drops(self):
         # The reference's in-block EIM-collision check is keyed by INTERNAL
-        # port (nat44.c:450-459), so plain reuse is a tolerated benign race;
-        # guaranteed exhaustion happens via the parity filter: a block with
+        # port (nat44.c:450-459), so a port comes round again after a full
+        # turn of the rotor while its first flow is still live: that reuse
+        # is tolerated and is no exhaustion.  (The wrap itself is exact, in
+        # the model and on the device: test_rotor_wrap_stays_in_block here,
+        # test_nat_port_rotor_gpu.py there.)
+        # Guaranteed exhaustion happens via the parity filter: a block with
         # only even ports + parity preservation + odd source port never
         # yields a port (64 tries, nat44.c:423-465).
         dp = nat_dp()
@@ -313,6 +317,24 @@ class TestNAT44:
         assert dp.nat44_egress(f) == DROP
         assert dp.nat_stats[abi.NS_PORT_EXHAUSTION] == 1
         assert dp.nat_log[-1]["event_type"] == abi.LOG_PORT_EXHAUSTION
+
+    @pytest.mark.parametrize("block", [(65520, 65535), (65535, 65535)],
+                             ids=["top16", "one-port-65535"])
+    def test_rotor_wrap_stays_in_block(self, block):
+        """_alloc_port on a block that ends at 65535, three full turns: the
+        counter's 16-bit truncation never shows as port 0 ("exhausted") or
+        as a port outside the block, the ports come in rotor order, and
+        next_port is inside the block after every call."""
+        dp = nat_dp()
+        blk = dp.subnat[ip2u32(PRIV)]
+        start, end = block
+        blk.port_start, blk.port_end, blk.next_port = start, end, start
+        size = end - start + 1
+        got = []
+        for _ in range(3 * size):
+            got.append(dp._alloc_port(blk, False, 40000, ip2u32(PRIV), 17))
+            assert start <= blk.next_port <= end
+        assert got == [start + k % size for k in range(3 * size)]
 
     def test_alg_trigger_punts(self):
         dp = nat_dp()

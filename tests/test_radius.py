@@ -119,6 +119,49 @@ class TestAccountingManager:
         assert rp.ACCT_INTERIM in types
         assert types[-1] == rp.ACCT_STOP
 
+    def test_no_interim_after_the_stop(self):
+        """The interim thread picks its due records and sends them
+        afterwards; a session stopped in between must not get an
+        Interim-Update behind its Stop.  And a Stop issued while an
+        Interim-Update of that session is on the wire goes out after it."""
+        import threading
+
+        class Wire:
+            def __init__(self):
+                self.sent, self.hold = [], threading.Event()
+                self.in_interim = threading.Event()
+
+            def send_accounting(self, status, sid, *a, **kw):
+                if status == rp.ACCT_INTERIM:
+                    self.in_interim.set()
+                    assert self.hold.wait(10)
+                self.sent.append((status, sid))
+                return True
+
+        w = Wire()
+        w.hold.set()
+        m = AccountingManager(w, interim_interval=3600)
+        sid = m.start_session("alice", session_id="s1")
+        picked = m.sessions[sid]             # what the interim loop holds
+        m.stop_session(sid)
+        m._send_interim(picked)
+        assert w.sent == [(rp.ACCT_START, "s1"), (rp.ACCT_STOP, "s1")]
+        assert not m.send_interim(sid)
+
+        w = Wire()
+        m = AccountingManager(w, interim_interval=3600)
+        sid = m.start_session("bob", session_id="s2")
+        t1 = threading.Thread(target=m.send_interim, args=(sid,))
+        t1.start()
+        assert w.in_interim.wait(10)         # the interim is on the wire
+        t2 = threading.Thread(target=m.stop_session, args=(sid,))
+        t2.start()
+        w.hold.set()
+        t1.join(10)
+        t2.join(10)
+        assert w.sent == [(rp.ACCT_START, "s2"), (rp.ACCT_INTERIM, "s2"),
+                          (rp.ACCT_STOP, "s2")]
+
     def test_pending_retry_after_partition(self, server):
         c = Client([server.addr], SECRET, timeout=0.2, retries=1)
         m = AccountingManager(c, interim_interval=3600,
