@@ -1728,8 +1728,31 @@ BNG_DEV bool qos_consume(int64_t* tokens, uint32_t pkt_len) {
   return false;
 }
 
+/* Refill credit min(floor(elapsed_ns * bytes_per_s / 1e9), cap), exact for
+ * every pair of 64-bit operands.  The product is taken in 128 bits and
+ * divided by long division in 32-bit digits: with hi < 1e9 every partial
+ * dividend is below 1e9 * 2^32 < 2^62.  A 64-bit product wraps from
+ * 14.76 s of idle time at 10 Gbps on.  cap fits 32 bits, so a quotient
+ * with a digit above the lowest is the cap.  Runs on the refill path only,
+ * which a packet reaches when its first consume failed. */
+BNG_DEV uint64_t qos_credit(uint64_t elapsed_ns, uint64_t bytes_per_s,
+                            uint32_t cap) {
+  const uint64_t D = 1000000000ull;
+  uint64_t hi = __umul64hi(elapsed_ns, bytes_per_s);
+  uint64_t lo = elapsed_ns * bytes_per_s;
+  if (hi >= D) return cap;               /* quotient >= 2^64 */
+  uint64_t d1 = (hi << 32) | (lo >> 32);
+  uint64_t q1 = d1 / D;
+  uint64_t d0 = ((d1 - q1 * D) << 32) | (lo & 0xFFFFFFFFull);
+  uint64_t q0 = d0 / D;                  /* d0 < 1e9 * 2^32: q0 < 2^32 */
+  return (q1 != 0 || q0 > cap) ? cap : q0;
+}
+
 /* field-pointer form so the standalone egress bucket (bng_qos_bucket)
- * and the merged uplink context (bng_subctx) share one implementation */
+ * and the merged uplink context (bng_subctx) share one implementation.
+ * Only a clock that moved forward refills: with now_ns <= last_update (a
+ * wall clock stepped back) there is no credit and the stamp stays, so
+ * credit resumes once the clock has caught up with it. */
 BNG_DEV bool qos_tb_check(int64_t* tokens, uint64_t* last_update,
                           uint32_t burst_bytes, uint32_t pkt_len,
                           uint64_t now_ns, uint64_t rate) {
@@ -1738,14 +1761,13 @@ BNG_DEV bool qos_tb_check(int64_t* tokens, uint64_t* last_update,
   /* insufficient: claim the refill, credit elapsed time, retry once */
   uint64_t last = __hip_atomic_load(last_update, __ATOMIC_RELAXED,
                                     __HIP_MEMORY_SCOPE_AGENT);
-  if (last != now_ns &&
+  if (last < now_ns &&
       __hip_atomic_compare_exchange_strong(
           last_update, &last, now_ns, __ATOMIC_RELAXED,
           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-    uint64_t elapsed = now_ns - last;
     int64_t burst = (int64_t)burst_bytes;
-    uint64_t add = (elapsed > 100000000000ull) ? (uint64_t)burst
-        : (elapsed * (rate / 8)) / 1000000000ull;
+    /* clamped to the burst while still unsigned: the cast cannot wrap */
+    uint64_t add = qos_credit(now_ns - last, rate / 8, burst_bytes);
     /* capped add, bounded CAS loop */
     for (int t = 0; t < 16; ++t) {
       int64_t cur = (int64_t)__hip_atomic_load(
@@ -2414,7 +2436,10 @@ __global__ void nat_sweep_kernel(bng_nat_session* sessions, uint32_t n_slots,
     if (sig == BNG_KEY_EMPTY || sig == BNG_KEY_TOMBSTONE || !s->ready)
       continue;
     /* fold the hot-path packed accounting deltas ({bytes:40,pkts:24} in
-     * _pad2[0/1]) into the u64 counters */
+     * _pad2[0/1]) into the u64 counters.  The packing bounds what one
+     * session may carry between two sweeps: 2^24 packets per direction
+     * (the 2^40 bytes hold 2^24 frames of 65535 B); past that the packet
+     * count carries into the byte field. */
     {
       unsigned long long po = atomicExch(
           (unsigned long long*)&s->_pad2[0], 0ull);
@@ -2434,9 +2459,13 @@ __global__ void nat_sweep_kernel(bng_nat_session* sessions, uint32_t n_slots,
       to = (s->state == BNG_NAT_ESTABLISHED) ? tcp_est_to : tcp_tr_to;
     else if (s->key.protocol == 1)
       to = icmp_to;
-    if (now_ns - s->last_seen < to && s->state != BNG_NAT_CLOSING) continue;
-    if (s->state == BNG_NAT_CLOSING && now_ns - s->last_seen < tcp_tr_to)
-      continue;
+    /* a session stamped after now_ns (a wall clock stepped back) has
+     * been idle for no time at all; the unsigned difference would wrap
+     * and expire every flow touched since */
+    uint64_t seen = s->last_seen;
+    uint64_t idle = now_ns > seen ? now_ns - seen : 0;
+    if (idle < to && s->state != BNG_NAT_CLOSING) continue;
+    if (s->state == BNG_NAT_CLOSING && idle < tcp_tr_to) continue;
     /* expire: tombstone session + its reverse entry, decrement counters */
     uint64_t rsig = bng_tuple_sig(s->key.dst_ip, s->nat_ip, s->key.dst_port,
                                   s->nat_port, s->key.protocol);
@@ -2465,7 +2494,8 @@ __global__ void nat_sweep_kernel(bng_nat_session* sessions, uint32_t n_slots,
       uint64_t sig = e->sig;
       if (sig == BNG_KEY_EMPTY || sig == BNG_KEY_TOMBSTONE || !e->ready)
         continue;
-      if (now_ns - e->last_used < eim_to)
+      uint64_t used = e->last_used;
+      if (now_ns <= used || now_ns - used < eim_to)   /* as above */
         continue;
       e->ready = 0;
       __hip_atomic_store(&e->sig, BNG_KEY_TOMBSTONE, __ATOMIC_RELAXED,

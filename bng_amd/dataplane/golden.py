@@ -697,14 +697,18 @@ class GoldenDataplane:
 
     # =========================================================== QoS K3
     def _tb_check(self, tb: QosBucketRec, pkt_len: int) -> bool:
-        """Token bucket (ref token_bucket_check qos_ratelimit.c:70-104)."""
+        """Token bucket (ref token_bucket_check qos_ratelimit.c:70-104).
+        Unlike the reference, a clock that has not moved past last_update
+        (a wall clock stepped back) earns nothing and leaves the stamp
+        alone, as on the device; the reference would subtract tokens."""
         if tb.rate_bps == 0:
             return True
         elapsed = self.now_ns - tb.last_update
-        tb.tokens += (elapsed * (tb.rate_bps // 8)) // 1_000_000_000
-        if tb.tokens > tb.burst_bytes:
-            tb.tokens = tb.burst_bytes
-        tb.last_update = self.now_ns
+        if elapsed > 0:
+            tb.tokens += (elapsed * (tb.rate_bps // 8)) // 1_000_000_000
+            if tb.tokens > tb.burst_bytes:
+                tb.tokens = tb.burst_bytes
+            tb.last_update = self.now_ns
         if tb.tokens >= pkt_len:
             tb.tokens -= pkt_len
             return True

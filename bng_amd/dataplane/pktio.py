@@ -95,15 +95,27 @@ def _concat_aranges(counts):
 def pack_frames(frames, stride: int):
     """Vectorized List[bytes] -> (data [n,stride] uint8, lens uint16).
 
-    The ingest half of the host edge: one join + fancy-index scatter,
-    no per-frame Python (round-1 VERDICT task 9)."""
+    The ingest half of the host edge: one join + one scatter, no
+    per-frame Python (round-1 VERDICT task 9).  While no frame is longer
+    than the stride the joined bytes are, in order, the bytes below each
+    row's length, so frames of one length are a reshape and mixed
+    lengths one boolean-mask store.  Index arrays (8 B of index per
+    payload byte, several times over) are left for a batch with a frame
+    to clip, or one so skewed that the n x longest mask would dwarf it."""
     import numpy as np
     n = len(frames)
-    lens = np.fromiter((len(f) for f in frames), dtype=np.int64, count=n)
-    clip = np.minimum(lens, stride)
+    lens = np.fromiter(map(len, frames), dtype=np.int64, count=n)
     joined = np.frombuffer(b"".join(frames), dtype=np.uint8)
-    offs = np.cumsum(lens) - lens               # frame starts in joined
     data = np.zeros((n, stride), dtype=np.uint8)
+    longest = int(lens.max()) if n else 0
+    if n and longest <= stride and n * longest <= 8 * joined.size:
+        if int(lens.min()) == longest:
+            data[:, :longest] = joined.reshape(n, longest)
+        else:
+            data[:, :longest][np.arange(longest) < lens[:, None]] = joined
+        return data, lens.astype(np.uint16)
+    clip = np.minimum(lens, stride)
+    offs = np.cumsum(lens) - lens               # frame starts in joined
     within = _concat_aranges(clip)
     dst = np.repeat(np.arange(n, dtype=np.int64) * stride, clip) + within
     src = np.repeat(offs, clip) + within

@@ -289,6 +289,37 @@ class TestPumpThroughput:
         assert (data[2] == 0).all()
         assert (data[3] == 3).all()
 
+    @pytest.mark.parametrize("shape", ["empty", "one-length", "mixed",
+                                       "zero-length", "full-stride",
+                                       "skewed", "clipped"])
+    def test_pack_frames_every_path_against_a_per_frame_copy(self, shape):
+        """pack_frames takes a reshape for frames of one length, a mask
+        store for mixed lengths and index arrays once a frame is clipped
+        or one frame is far longer than the rest;
+        each must equal the plain per-frame copy, byte for byte."""
+        import random
+        from bng_amd.dataplane.pktio import pack_frames
+        rng = random.Random(shape)
+        stride = 96
+        sizes = {"empty": [], "one-length": [64] * 37,
+                 "mixed": [rng.randint(1, 95) for _ in range(70)],
+                 "zero-length": [0, 0, 0],
+                 "full-stride": [96, 1, 0, 96, 95],
+                 "skewed": [2] * 70 + [96],
+                 "clipped": [rng.randint(0, 200) for _ in range(70)] + [97]
+                 }[shape]
+        frames = [bytes(rng.randrange(256) for _ in range(L)) for L in sizes]
+        data, lens = pack_frames(frames, stride)
+        want = np.zeros((len(frames), stride), dtype=np.uint8)
+        for i, f in enumerate(frames):
+            want[i, :min(len(f), stride)] = np.frombuffer(
+                f[:stride], dtype=np.uint8)
+        assert data.shape == want.shape and data.dtype == np.uint8
+        assert lens.dtype == np.uint16
+        assert lens.tolist() == [min(L, stride) for L in sizes]
+        assert (data == want).all()
+        assert data.flags.writeable and data.flags.c_contiguous
+
 
 class TestDownlinkPump:
     """Core-side pump: NAT44 DNAT -> QoS-egress (ref tc_egress, tc.c).

@@ -361,9 +361,10 @@ def flow_frame(k, i=0):
                       payload=b"\x00" * ((k % 5) * 7))
 
 
-def session_table(gpu):
+def session_table(gpu, inbound=False):
     """{tuple: (nat_ip, nat_port, last_seen, created, pkts_out, bytes_out)}
-    from the raw device table, packed accounting deltas folded in."""
+    from the raw device table, packed accounting deltas folded in; with
+    inbound, each row goes on with (state, pkts_in, bytes_in)."""
     arr = gpu.sessions.cpu().numpy().view(
         [("sig", "<u8"), ("src_ip", "<u4"), ("dst_ip", "<u4"),
          ("src_port", "<u2"), ("dst_port", "<u2"), ("protocol", "u1"),
@@ -385,12 +386,19 @@ def session_table(gpu):
                     int(e["last_seen"]), int(e["created"]),
                     int(e["packets_out"]) + (acct & 0xFFFFFF),
                     int(e["bytes_out"]) + (acct >> 24))
+        if inbound:
+            acct = int(e["acct_in"])
+            out[key] += (int(e["state"]),
+                         int(e["packets_in"]) + (acct & 0xFFFFFF),
+                         int(e["bytes_in"]) + (acct >> 24))
     return out
 
 
-def golden_session_table(cpu):
+def golden_session_table(cpu, inbound=False):
     return {k: (s.nat_ip, s.nat_port, s.last_seen, s.created, s.packets_out,
-                s.bytes_out) for k, s in cpu.dp.nat_sessions.items()}
+                s.bytes_out) +
+            ((s.state, s.packets_in, s.bytes_in) if inbound else ())
+            for k, s in cpu.dp.nat_sessions.items()}
 
 
 def sorted_export(l):
