@@ -177,6 +177,10 @@ def build_parser() -> argparse.ArgumentParser:
                    ("false", "0", "no", False))
     g.add_argument("--nat-hairpin", default=True, type=lambda v: v not in
                    ("false", "0", "no", False))
+    g.add_argument("--nat-icmp-errors", default=False, nargs="?", const=True,
+                   type=lambda v: v in ("true", "1", "yes", True),
+                   help="translate inbound ICMP errors about subscriber "
+                        "flows (RFC 5508); bare or with true/false")
     g.add_argument("--nat-alg-ftp", default=True, type=lambda v: v not in
                    ("false", "0", "no", False))
     g.add_argument("--nat-alg-sip", default=False, type=lambda v: v in
@@ -721,6 +725,8 @@ class BNG:
                 natflags |= _abi.NAT_FLAG_EIF
             if a.nat_hairpin:
                 natflags |= _abi.NAT_FLAG_HAIRPIN
+            if a.nat_icmp_errors:
+                natflags |= _abi.NAT_FLAG_ICMP_ERR
             if a.nat_alg_ftp:
                 natflags |= _abi.NAT_FLAG_ALG_FTP
                 alg_ports.append((21, 6))

@@ -65,6 +65,7 @@ NAT_FLAG_ALG_FTP = 0x08
 NAT_FLAG_ALG_SIP = 0x10
 NAT_FLAG_PARITY = 0x20
 NAT_FLAG_CONTIG = 0x40
+NAT_FLAG_ICMP_ERR = 0x80    # translate inbound ICMP errors (RFC 5508)
 
 # NAT states (ref nat44.c:65-71)
 NAT_NEW, NAT_ESTABLISHED, NAT_FIN_WAIT, NAT_CLOSING, NAT_TIME_WAIT = range(5)
@@ -72,13 +73,15 @@ NAT_NEW, NAT_ESTABLISHED, NAT_FIN_WAIT, NAT_CLOSING, NAT_TIME_WAIT = range(5)
 # NAT stat indices (ref nat44.c:176-190)
 NS_SNAT, NS_DNAT, NS_HAIRPIN, NS_DROPPED, NS_PASSED, NS_SESS_CREATED, \
     NS_SESS_EXPIRED, NS_PORT_EXHAUSTION, NS_EIM_HITS, NS_EIM_MISSES, \
-    NS_ALG_TRIGGERS, NS_CT_LOOKUPS, NS_CT_HITS = range(13)
-NAT_NSTATS = 13
+    NS_ALG_TRIGGERS, NS_CT_LOOKUPS, NS_CT_HITS, NS_ICMP_ERR_XLATE, \
+    NS_ICMP_ERR_NOMAP = range(15)
+NAT_NSTATS = 15
 NAT_STAT_NAMES = [
     "packets_snat", "packets_dnat", "packets_hairpin", "packets_dropped",
     "packets_passed", "sessions_created", "sessions_expired",
     "port_exhaustion", "eim_hits", "eim_misses", "alg_triggers",
     "conntrack_lookups", "conntrack_hits",
+    "icmp_errors_translated", "icmp_errors_unmatched",
 ]
 
 # NAT log events (ref nat44.c:74-82)

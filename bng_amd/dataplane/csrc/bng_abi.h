@@ -222,6 +222,7 @@ typedef struct bng_subctx {
 #define BNG_NAT_FLAG_ALG_SIP   0x10
 #define BNG_NAT_FLAG_PARITY    0x20
 #define BNG_NAT_FLAG_CONTIG    0x40
+#define BNG_NAT_FLAG_ICMP_ERR  0x80  /* translate inbound ICMP errors (RFC 5508) */
 
 typedef struct bng_nat_config {
   uint32_t flags;
@@ -246,6 +247,8 @@ enum bng_nat_stat {  /* ref nat_stats nat44.c:176-190 */
   BNG_NS_SESS_CREATED, BNG_NS_SESS_EXPIRED, BNG_NS_PORT_EXHAUSTION,
   BNG_NS_EIM_HITS, BNG_NS_EIM_MISSES, BNG_NS_ALG_TRIGGERS,
   BNG_NS_CT_LOOKUPS, BNG_NS_CT_HITS,
+  /* no reference analog: inbound ICMP errors under BNG_NAT_FLAG_ICMP_ERR */
+  BNG_NS_ICMP_ERR_XLATE, BNG_NS_ICMP_ERR_NOMAP,
   BNG_NAT_NSTATS
 };
 

@@ -1166,10 +1166,10 @@ struct nat_tables {
 
 struct nat_flags {
   bool snat, dnat, hairpin, dropped, passed, sess_created, sess_expired,
-       port_exh, eim_hit, eim_miss, alg;
+       port_exh, eim_hit, eim_miss, alg, icmp_xlate, icmp_nomap;
   BNG_DEV void clear() {
     snat = dnat = hairpin = dropped = passed = sess_created = sess_expired =
-        port_exh = eim_hit = eim_miss = alg = false;
+        port_exh = eim_hit = eim_miss = alg = icmp_xlate = icmp_nomap = false;
   }
 };
 
@@ -1550,6 +1550,125 @@ BNG_DEV int nat_egress_process(pktctx& c, const nat_tables& T,
   return nat_egress_ctx(c, T, F, h.e, h.nat_valid);
 }
 
+/* What nat_ingress_icmp_error did with the frame */
+enum { ICMP_ERR_IGNORED = 0, ICMP_ERR_XLATE = 1, ICMP_ERR_NOMAP = 2 };
+
+/* Inbound ICMP error to a public address (RFC 5508 REQ-3/4/5; no reference
+ * analog: nat44.c:644-648 reads bytes 4..5 of an error as an echo id).  A
+ * Destination Unreachable (3), Time Exceeded (11) or Parameter Problem (12)
+ * quotes the datagram it is about, as the NAT sent it: the quoted source is
+ * the public address and port.  The quote's flow is looked up the way DNAT
+ * looks up a reply (reverse entry -> session), then the outer destination
+ * and the quoted source address and port (or query id) become the
+ * subscriber's, with every checksum that covers a changed word updated
+ * incrementally — the quoted IP header's, the quoted L4's where its field
+ * is inside the frame, and the outer ICMP's for each of those words.
+ *
+ * Reads the tables, writes none: an error neither refreshes last_seen nor
+ * counts as session traffic, moves no TCP state and tombstones no stale
+ * reverse entry (the next ordinary packet does that).  Every load and store
+ * is a byte access below `len`.
+ *
+ * Cold (one call per error frame), so a real call, out of line: the DNAT
+ * hit path keeps its registers.  The arguments are values on purpose — a
+ * reference to the parsed context or to the flags would take their address
+ * and put the context's register window into scratch memory in both
+ * callers.  Returns ICMP_ERR_*; IGNORED is every frame this stage forwards
+ * unread today and still does (a non-first fragment, fewer than 8 bytes of
+ * ICMP, any other type). */
+__device__ __noinline__ int nat_ingress_icmp_error(
+    uint8_t* p, int len, int ip_off, int l4_off, uint32_t daddr,
+    bng_nat_reverse* reverse, uint32_t rev_mask,
+    bng_nat_session* sessions, uint32_t sess_mask) {
+  if (ld_u16be(p + ip_off + 6) & 0x1FFF) return ICMP_ERR_IGNORED;
+  if (len < l4_off + 8) return ICMP_ERR_IGNORED;
+  uint32_t type = p[l4_off];
+  if (type != 3 && type != 11 && type != 12) return ICMP_ERR_IGNORED;
+
+  /* the quoted datagram: header at e, its first 8 L4 bytes at q */
+  int e = l4_off + 8;
+  if (len < e + 20) return ICMP_ERR_NOMAP;
+  uint32_t vihl = p[e];
+  if ((vihl >> 4) != 4 || (vihl & 0xF) < 5) return ICMP_ERR_NOMAP;
+  int q = e + (int)(vihl & 0xF) * 4;
+  if (len < q + 8) return ICMP_ERR_NOMAP;
+  if (ld_u16be(p + e + 6) & 0x1FFF) return ICMP_ERR_NOMAP;
+  uint32_t pub_ip = ld_u32be(p + e + 12), remote_ip = ld_u32be(p + e + 16);
+  if (pub_ip != daddr) return ICMP_ERR_NOMAP;
+  uint32_t proto = p[e + 9];
+  int id_at;                       /* the public port or id inside the quote */
+  uint16_t sport;                  /* reverse key: the remote end's port */
+  if (proto == 6 || proto == 17) {
+    id_at = q; sport = ld_u16be(p + q + 2);
+  } else if (proto == 1 && icmp_is_query(p[q])) {
+    id_at = q + 4; sport = 0;
+  } else return ICMP_ERR_NOMAP;
+  uint16_t pub_port = ld_u16be(p + id_at);
+
+  /* reverse entry -> session, with DNAT's checks and none of its writes */
+  uint64_t rsig = bng_tuple_sig(remote_ip, pub_ip, sport, pub_port,
+                                (uint8_t)proto);
+  bng_nat_reverse* rev = sig_lookup(reverse, rev_mask, rsig);
+  if (!rev || !bng_wait_ready(&rev->ready, 8192)) return ICMP_ERR_NOMAP;
+  const uint64_t* r64 = (const uint64_t*)rev;
+  uint64_t k0 = rlx_load64(r64 + 1), k1 = rlx_load64(r64 + 2);
+  uint64_t ek0 = ((uint64_t)pub_ip << 32) | remote_ip;
+  uint64_t ek1 = (uint64_t)sport | ((uint64_t)pub_port << 16) |
+                 ((uint64_t)proto << 32);
+  if (k0 != ek0 || (k1 & 0xFFFFFFFFFFull) != ek1) return ICMP_ERR_NOMAP;
+  bng_nat_tuple orig;
+  uint64_t o0 = rlx_load64(r64 + 3), o1 = rlx_load64(r64 + 4);
+  orig.src_ip = (uint32_t)o0; orig.dst_ip = (uint32_t)(o0 >> 32);
+  orig.src_port = (uint16_t)o1; orig.dst_port = (uint16_t)(o1 >> 16);
+  orig.protocol = (uint8_t)(o1 >> 32);
+  uint64_t osig = bng_tuple_sig(orig.src_ip, orig.dst_ip, orig.src_port,
+                                orig.dst_port, orig.protocol);
+  const bng_nat_session* sess = sig_lookup(sessions, sess_mask, osig);
+  if (!sess || !bng_wait_ready(&sess->ready, 8192) ||
+      !tuple_eq(sess->key, orig))
+    return ICMP_ERR_NOMAP;
+  uint32_t new_ip = sess->orig_ip;
+  uint16_t new_port = sess->orig_port;
+
+  /* 1. outer destination, outer header checksum */
+  st_u32be(p + ip_off + 16, new_ip);
+  st_u16be(p + ip_off + 10,
+           csum_upd32(ld_u16be(p + ip_off + 10), pub_ip, new_ip));
+  /* the outer ICMP checksum follows every quoted word that changes */
+  uint16_t ock = ld_u16be(p + l4_off + 2);
+  /* 2. quoted source, quoted header checksum */
+  st_u32be(p + e + 12, new_ip);
+  ock = csum_upd32(ock, pub_ip, new_ip);
+  {
+    uint16_t ck = ld_u16be(p + e + 10);
+    uint16_t nk = csum_upd32(ck, pub_ip, new_ip);
+    st_u16be(p + e + 10, nk);
+    ock = csum_upd16(ock, ck, nk);
+  }
+  /* 3. quoted source port or id */
+  st_u16be(p + id_at, new_port);
+  ock = csum_upd16(ock, pub_port, new_port);
+  /* 4. quoted L4 checksum, where the quote reaches it */
+  int ck_at = proto == 6 ? q + 16 : proto == 17 ? q + 6 : q + 2;
+  if (len >= ck_at + 2) {
+    uint16_t ck = ld_u16be(p + ck_at), nk = ck;
+    if (proto == 1) {
+      nk = csum_upd16(ck, pub_port, new_port);
+    } else if (proto == 6 || ck != 0) {      /* UDP 0: sender computed none */
+      nk = csum_upd32(ck, pub_ip, new_ip);
+      nk = csum_upd16(nk, pub_port, new_port);
+      if (proto == 17 && nk == 0) nk = 0xFFFF;
+    }
+    if (nk != ck) {
+      st_u16be(p + ck_at, nk);
+      ock = csum_upd16(ock, ck, nk);
+    }
+  }
+  /* 5. outer ICMP checksum */
+  st_u16be(p + l4_off + 2, ock);
+  return ICMP_ERR_XLATE;
+}
+
 /* DNAT (ref nat44_ingress nat44.c:805-948) */
 BNG_DEV int nat_ingress_process(pktctx& c, const nat_tables& T, nat_flags& F) {
   uint8_t* p = c.p;
@@ -1559,7 +1678,16 @@ BNG_DEV int nat_ingress_process(pktctx& c, const nat_tables& T, nat_flags& F) {
     if (!c.l4_ok) return BNG_FWD;
     sport = c.sport; dport = c.dport;
   } else if (c.proto == 1) {
-    if (!c.l4_ok) return BNG_FWD;
+    if (!c.l4_ok) {
+      if (T.cfg->flags & BNG_NAT_FLAG_ICMP_ERR) {
+        int r = nat_ingress_icmp_error(p, c.len, c.ip_off, c.l4_off, c.daddr,
+                                       T.reverse, T.rev_mask, T.sessions,
+                                       T.sess_mask);
+        F.icmp_xlate = r == ICMP_ERR_XLATE;
+        F.icmp_nomap = r == ICMP_ERR_NOMAP;
+      }
+      return BNG_FWD;
+    }
     sport = 0; dport = c.icmp_id;
   } else return BNG_FWD;
 
@@ -1658,9 +1786,14 @@ BNG_DEV void nat_count_stats(const nat_flags& F, unsigned long long* sb) {
   sb_fold(sb, SB_NAT + BNG_NS_EIM_HITS, wave_count(F.eim_hit));
   sb_fold(sb, SB_NAT + BNG_NS_EIM_MISSES, wave_count(F.eim_miss));
   sb_fold(sb, SB_NAT + BNG_NS_ALG_TRIGGERS, wave_count(F.alg));
+  sb_fold(sb, SB_NAT + BNG_NS_ICMP_ERR_XLATE, wave_count(F.icmp_xlate));
+  sb_fold(sb, SB_NAT + BNG_NS_ICMP_ERR_NOMAP, wave_count(F.icmp_nomap));
 }
 
-__global__ void nat44_kernel(
+/* the bound keeps the 5 waves per SIMD the kernel had before the out-of-line
+ * ICMP-error call: values that live across a call sit in the callee-saved
+ * ranges, which spreads the allocation to 102 VGPRs without it, 96 with */
+__global__ __launch_bounds__(256, 5) void nat44_kernel(
     uint8_t* __restrict__ data, const uint16_t* __restrict__ in_len,
     uint8_t* __restrict__ verdict, int n, int stride, int is_egress,
     bng_nat_session* sessions, uint32_t sess_mask,

@@ -625,7 +625,11 @@ class GoldenDataplane:
         """DNAT (ref nat44_ingress nat44.c:805-948).  Unlike the reference,
         non-first fragments and non-query ICMP are forwarded unread."""
         h = self._parse_l3l4(frame)
-        if h is None or h["no_l4"] or h["short"]:
+        if h is None:
+            return FWD
+        if h["no_l4"] or h["short"]:
+            if h["proto"] == 1 and self.nat_flags & abi.NAT_FLAG_ICMP_ERR:
+                self._nat44_ingress_icmp_error(frame, h)
             return FWD
         proto = h["proto"]
         if proto == 6 or proto == 17:
@@ -686,6 +690,88 @@ class GoldenDataplane:
                              self._upd_csum16(ck, old_id, new_port))
         self.nat_stats[abi.NS_DNAT] += 1
         return FWD
+
+    def _nat44_ingress_icmp_error(self, frame: bytearray, h: dict) -> None:
+        """An inbound ICMP message DNAT forwards unread, under
+        NAT_FLAG_ICMP_ERR (RFC 5508 REQ-3/4/5; nat_ingress_icmp_error in
+        the kernels).  A Destination Unreachable, Time Exceeded or Parameter
+        Problem whose quoted datagram is a flow of ours gets the outer
+        destination and the quoted source address and port (or query id)
+        set back to the subscriber's, every checksum over a changed word
+        updated incrementally.  Reads the tables and writes none of them:
+        no last_seen, no counters or state of the session, no cleaning of a
+        stale reverse entry.  The verdict is FWD whatever happens here."""
+        n, ip_off, l4 = len(frame), h["ip_off"], h["l4"]
+        u16 = lambda o: struct.unpack_from(">H", frame, o)[0]
+        if u16(ip_off + 6) & 0x1FFF or n < l4 + 8 or \
+                frame[l4] not in (3, 11, 12):
+            return                     # as with the flag off: not counted
+        hit = self._icmp_error_flow(frame, h["daddr"], l4 + 8)
+        if hit is None:
+            self.nat_stats[abi.NS_ICMP_ERR_NOMAP] += 1
+            return
+        e, q, proto, id_at, pub_ip, pub_port, sess = hit
+        new_ip, new_port = sess.orig_ip, sess.orig_port
+        put16 = lambda o, v: struct.pack_into(">H", frame, o, v)
+        # 1. outer destination and header checksum
+        struct.pack_into(">I", frame, ip_off + 16, new_ip)
+        put16(ip_off + 10, self._upd_csum(u16(ip_off + 10), pub_ip, new_ip))
+        ock = u16(l4 + 2)              # follows every quoted word that changes
+        # 2. quoted source and header checksum
+        struct.pack_into(">I", frame, e + 12, new_ip)
+        ock = self._upd_csum(ock, pub_ip, new_ip)
+        ck = u16(e + 10)
+        nk = self._upd_csum(ck, pub_ip, new_ip)
+        put16(e + 10, nk)
+        ock = self._upd_csum16(ock, ck, nk)
+        # 3. quoted source port or id
+        put16(id_at, new_port)
+        ock = self._upd_csum16(ock, pub_port, new_port)
+        # 4. quoted L4 checksum, where the quote reaches it
+        ck_at = q + {6: 16, 17: 6, 1: 2}[proto]
+        if n >= ck_at + 2:
+            ck = nk = u16(ck_at)
+            if proto == 1:
+                nk = self._upd_csum16(ck, pub_port, new_port)
+            elif proto == 6 or ck != 0:
+                nk = self._upd_csum(ck, pub_ip, new_ip)
+                nk = self._upd_csum16(nk, pub_port, new_port)
+                if proto == 17 and nk == 0:
+                    nk = 0xFFFF
+            if nk != ck:
+                put16(ck_at, nk)
+                ock = self._upd_csum16(ock, ck, nk)
+        # 5. outer ICMP checksum
+        put16(l4 + 2, ock)
+        self.nat_stats[abi.NS_ICMP_ERR_XLATE] += 1
+
+    def _icmp_error_flow(self, frame, outer_daddr: int, e: int):
+        """The session the datagram quoted at `e` belongs to, or None:
+        (e, quoted L4 offset, protocol, offset of the public port or id,
+        public ip, public port or id, session)."""
+        n = len(frame)
+        if n < e + 20 or not self._ipv4_header_ok(frame, e):
+            return None
+        q = e + (frame[e] & 0xF) * 4
+        if n < q + 8 or struct.unpack_from(">H", frame, e + 6)[0] & 0x1FFF:
+            return None
+        pub_ip, remote_ip = struct.unpack_from(">II", frame, e + 12)
+        if pub_ip != outer_daddr:
+            return None
+        proto = frame[e + 9]
+        if proto in (6, 17):
+            id_at, sport = q, struct.unpack_from(">H", frame, q + 2)[0]
+        elif proto == 1 and frame[q] in ICMP_QUERY_TYPES:
+            id_at, sport = q + 4, 0
+        else:
+            return None
+        pub_port = struct.unpack_from(">H", frame, id_at)[0]
+        orig_key = self.nat_reverse.get(
+            (remote_ip, pub_ip, sport, pub_port, proto))
+        sess = self.nat_sessions.get(orig_key) if orig_key else None
+        if sess is None:
+            return None
+        return e, q, proto, id_at, pub_ip, pub_port, sess
 
     def _log(self, ev, sub_id, priv_ip, pub_ip, priv_port, pub_port,
              dest_ip, dest_port, proto, flags=0):

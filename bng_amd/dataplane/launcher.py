@@ -773,8 +773,11 @@ class HipLauncher:
             self.acct_launches["commit"] += 1
         return verdict, out_len
 
-    def downlink(self, data, lens, now_ns: Optional[int] = None):
-        """Fused NAT44 DNAT -> QoS-egress return path.  With PPPoE sessions
+    def downlink(self, data, lens, now_ns: Optional[int] = None,
+                 order=None):
+        """Fused NAT44 DNAT -> QoS-egress return path.  `order`, a
+        permutation of the rows as int32, is the dispatch order (which lane
+        takes which row), as for uplink().  With PPPoE sessions
         provisioned, pppoe_encap() follows: `lens` is updated in place and
         the state stays reachable as last_pppoe_state.  With accounting
         entries live, acct_downlink bills the frames in between.  With
@@ -791,7 +794,7 @@ class HipLauncher:
             self.reverse, self.eim, self.subctx, self.nat_cfg, self.hairpin,
             self.n_hairpin, self.nat_stats, self.nat_log_ring,
             self.nat_log_hdr, self.qos_egress, self.qos_stats, now,
-            now // 10**9, order=None, downlink=True,
+            now // 10**9, order=order, downlink=True,
             masked=self.masked_compute)
         if self._wg_live and n:
             gate = self.torch.empty(n, dtype=self.torch.uint8,

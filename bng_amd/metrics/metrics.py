@@ -59,6 +59,10 @@ class Metrics:
         self.nat_port_exhaustion = Gauge(
             "bng_nat_port_exhaustion_total", "port exhaustion events",
             registry=r)
+        self.nat_icmp_errors = Gauge(
+            "bng_nat_icmp_errors_total",
+            "inbound ICMP errors met by NAT44 with ICMP-error translation on",
+            ["result"], registry=r)
         # RADIUS
         self.radius_requests = Counter(
             "bng_radius_requests_total", "RADIUS ops", ["op", "result"],
@@ -171,6 +175,9 @@ class Metrics:
                 self.dataplane_stat.labels("nat", name).set(v)
             self.nat_port_exhaustion.set(
                 launcher.nat_get_stats().get("port_exhaustion", 0))
+            for result in ("translated", "unmatched"):
+                self.nat_icmp_errors.labels(result).set(
+                    launcher.nat_get_stats().get("icmp_errors_" + result, 0))
             for name, v in launcher.qos_get_stats().items():
                 self.dataplane_stat.labels("qos", name).set(v)
             self.qos_dropped.set(

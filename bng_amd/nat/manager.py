@@ -78,6 +78,15 @@ class Manager:
             self.flags &= ~abi.NAT_FLAG_HAIRPIN
         self._push_config()
 
+    def enable_icmp_errors(self, enabled: bool = True):
+        """Translate inbound ICMP errors about a subscriber's flows
+        (RFC 5508 REQ-3/4/5).  Off unless asked for."""
+        if enabled:
+            self.flags |= abi.NAT_FLAG_ICMP_ERR
+        else:
+            self.flags &= ~abi.NAT_FLAG_ICMP_ERR
+        self._push_config()
+
     def _push_config(self):
         if self.launcher is None:
             return
